@@ -1,7 +1,7 @@
 # Convenience targets (reference-repo Makefile parity).
 PY ?= python3
 
-.PHONY: build test test-gpu race bench smoke clean
+.PHONY: build test test-gpu race bench bench-full smoke clean
 
 build:
 	$(PY) -c "from llm_d_kv_cache_amd._build import build_all; build_all()"
@@ -18,6 +18,10 @@ race:
 
 bench: build
 	$(PY) bench.py --steps 12 --warmup 3
+
+# headline + aux phases (control plane, peer pulls, storage-tier variants)
+bench-full: build
+	$(PY) bench.py --steps 12 --warmup 3 --full
 
 smoke: build
 	$(PY) -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"

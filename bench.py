@@ -8,11 +8,17 @@ the previous generation. The headline value is the whole-job aggregate
 offload throughput in GB/s across all ranks (weak scaling: per-GPU work is
 fixed).
 
-Score() and KVEvents-ingest rates — the control-plane north-star metrics —
-are measured in separate bracketed phases and reported as aux fields.
+A plain run does only what the headline needs: set up, warm up, time the
+K steps, print the JSON result line. `--full` adds the aux phases after the
+timed region, each bracketed on its own and reported under `aux`: Score()
+and KVEvents-ingest rates (the control-plane north-star metrics), the xGMI
+peer-pull phase when N > 1, and the storage-tier variants (DRAM tier off,
+real NVMe). `--dump-outputs DIR` writes what the last timed step handed its
+callers as DIR/<name>.npy (float32); the KV pages are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Launch (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -414,6 +420,67 @@ def bench_peer_phase(dist, torch, group, rank, world, local_rank):
     return out
 
 
+def dump_outputs(out_dir, group, mapper, last_out, rank, world):
+    """--dump-outputs: what the LAST timed step handed its callers, as
+    float32 .npy files (byte values 0..255, exact in float32).
+
+      loaded_kv.npy          (layers, n, block_bytes): the GPU pages the
+                             step's load scattered into, for a fixed seeded
+                             sample of n blocks (first and last included)
+      stored_file_first.npy  (k, 4096): a fixed seeded sample of 4 KiB
+      stored_file_last.npy   chunks of the first / last KV file the step's
+                             store wrote
+
+    The sample keeps the dump under ~40 MB whatever the preset; ranks of a
+    multi-rank run write <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    rng = np.random.default_rng(0)
+
+    load_ids = last_out.get("load_ids")
+    if load_ids:
+        budget = 8 << 20  # sampled KV bytes; x4 once widened to float32
+        n = max(1, min(len(load_ids), budget // (len(group) * BLOCK_BYTES)))
+        pick = np.sort(rng.choice(len(load_ids), size=n, replace=False))
+        pick[0] = 0
+        if n > 1:
+            pick[-1] = len(load_ids) - 1
+        idx = torch.tensor([load_ids[i] for i in pick], dtype=torch.long,
+                           device=group[0].device)
+        arr = np.stack([t.index_select(0, idx).cpu().numpy() for t in group])
+        np.save(os.path.join(out_dir, f"loaded_kv{suffix}.npy"),
+                arr.astype(np.float32))
+    else:
+        log("dump-outputs: the last timed step loaded nothing "
+            "(--steps 0, or --steps 1 with --warmup 0)")
+
+    hashes = last_out.get("store_hashes") or []
+    for name, h in (("first", hashes[:1]), ("last", hashes[-1:])):
+        if not h:
+            continue
+        path = mapper.file_name(h[0], 0)
+        try:
+            size = os.path.getsize(path)
+            n_chunks = max(1, size // 4096)
+            pick = np.sort(rng.choice(n_chunks, size=min(256, n_chunks),
+                                      replace=False))
+            rows = np.zeros((len(pick), 4096), dtype=np.uint8)
+            with open(path, "rb") as f:
+                for r, c in enumerate(pick):
+                    f.seek(int(c) * 4096)
+                    buf = f.read(4096)
+                    rows[r, :len(buf)] = np.frombuffer(buf, dtype=np.uint8)
+        except OSError as e:  # e.g. write-back: not flushed to a file yet
+            log(f"dump-outputs: stored file {path} unreadable: {e}")
+            continue
+        np.save(os.path.join(out_dir, f"stored_file_{name}{suffix}.npy"),
+                rows.astype(np.float32))
+    log(f"outputs dumped to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,6 +521,15 @@ def main():
                          "drain (within noise of 1 when the DRAM tier "
                          "covers the window — profiles/r02_offload.md). "
                          "All work completes inside the timed region.")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the aux phases "
+                         "(control-plane Score()/ingest rates, xGMI peer "
+                         "pulls when N > 1, DRAM-tier-off and NVMe "
+                         "variants) and report them under `aux`")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step produced (sampled "
+                         "loaded KV pages + stored-file bytes) as "
+                         "DIR/<name>.npy, float32")
     args = ap.parse_args()
     apply_model_preset(args.model)
     if args.host_cache_gb is None:
@@ -494,8 +570,11 @@ def main():
     gpu = torch.cuda.is_available()
     cpu_full = bool(os.environ.get("KVC_BENCH_CPU_FULL"))
     if not gpu and not cpu_full:
-        log("no GPU: control-plane phases only; offload GB/s unmeasured")
-        aux = bench_control_plane()
+        log("no GPU: offload GB/s unmeasured; control-plane phases run "
+            "under --full only")
+        if args.dump_outputs:
+            log("dump-outputs: no timed offload steps ran, nothing to dump")
+        aux = bench_control_plane() if args.full else None
         if rank == 0:
             print(json.dumps({
                 "metric": "kv_block_offload_GBps", "value": None, "unit": "GB/s",
@@ -539,6 +618,9 @@ def main():
     log(f"allocating KV cache: {args.device_blocks} blocks x {NUM_LAYERS} layers "
         f"x {BLOCK_BYTES // 1024} KiB = "
         f"{args.device_blocks * NUM_LAYERS * BLOCK_BYTES / 1e9:.1f} GB")
+    # seeded (per rank): same arguments -> same pages, run after run, so
+    # --dump-outputs of two builds compare value for value
+    torch.manual_seed(1234 + rank)
     group = [
         torch.randint(0, 255, (args.device_blocks, BLOCK_BYTES), dtype=torch.uint8,
                       device="cuda" if gpu else "cpu")
@@ -567,6 +649,7 @@ def main():
 
     phase_wall = {"store": 0.0, "load": 0.0, "unlink": 0.0}
     moved = {"bytes": 0}  # actual store+load volume issued in timed steps
+    last_out = {}  # the latest step's stored hashes + loaded page ids
 
     # Background deleters: steady-state disk management runs concurrently
     # with serving (the evictor's job in production), not on the hot path.
@@ -634,6 +717,7 @@ def main():
         all_ids = list(range(blocks_per_step))
         store_jobs[step_id] = store.transfer_async(hashes, {0: all_ids})
         pending["n"] += 1
+        lids = None
         if do_load:
             await_store(load_gen)
             off = blocks_per_step
@@ -642,6 +726,7 @@ def main():
             lids = [b + off for b in all_ids]
             load.transfer_async(prev_hashes, {0: lids})
             pending["n"] += 1
+        last_out["store_hashes"], last_out["load_ids"] = hashes, lids
         # steady-state window: at most `pipeline` steps of jobs in flight
         drain_to(2 * (args.pipeline - 1))
         p1 = time.perf_counter()
@@ -682,6 +767,7 @@ def main():
             if done < n_jobs:
                 time.sleep(0.0002)
         p2 = time.perf_counter()
+        last_out["store_hashes"], last_out["load_ids"] = hashes, ids
         if step_id >= 0:
             moved["bytes"] += 2 * step_bytes
         # drop the previous generation in the background (evictor's role)
@@ -720,6 +806,7 @@ def main():
     while not del_q.empty():
         time.sleep(0.005)
     log("warmup done")
+    last_out.clear()
 
     barrier()
     t0 = time.perf_counter()
@@ -748,12 +835,17 @@ def main():
     moved_bytes = moved["bytes"]
     total_gbps = moved_bytes * world / elapsed / 1e9
     stats = eng.stats()
+    _trace(rank, "main: timed steps done")
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, group, mapper, last_out, rank, world)
+
+    # Everything from here to the result line is aux and runs under --full
+    # only; a plain run goes straight to cleanup + the result line.
     # xGMI peer-migration phase (aux, outside the headline timed region):
     # each rank pulls its neighbor's cached chunks over RCCL send/recv.
-    _trace(rank, "main: timed steps done")
     peer_aux = None
-    if world > 1 and dist is not None:
+    if args.full and world > 1 and dist is not None:
         try:
             peer_aux = bench_peer_phase(dist, torch, group, rank, world,
                                         local_rank)
@@ -762,7 +854,7 @@ def main():
             peer_aux = {"ok": False, "error": str(e)}
 
     _trace(rank, "main: peer phase done")
-    aux = bench_control_plane() if rank == 0 else None
+    aux = bench_control_plane() if args.full and rank == 0 else None
     _trace(rank, "main: control plane done")
     if aux is not None and peer_aux is not None:
         aux["peer_xgmi"] = peer_aux
@@ -804,7 +896,7 @@ def main():
             "n_gpus": world if gpu else 0,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+            "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 2),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

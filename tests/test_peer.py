@@ -431,6 +431,9 @@ def scenario_mesh_pull_world4(rank, svc, group):
     for src, (dst, f) in futs.items():
         assert f.result(timeout=150) is True, f"pull from {src} failed"
         assert torch.equal(group[0][dst], goldens[src])
+    # only once EVERY rank's pulls are done has this rank certainly served
+    # one: its own pulls can all finish before any peer has pulled from it
+    dist.barrier()
     assert svc.stats().pulls_served >= 1
     dist.barrier()
 
