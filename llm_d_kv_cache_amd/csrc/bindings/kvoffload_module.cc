@@ -56,7 +56,8 @@ PYBIND11_MODULE(_kvoffload, m) {
                        double read_preferring_ratio, double max_write_queued_seconds,
                        bool gpu_mode, int device, const std::string& copy_path,
                        const std::string& serialize, size_t host_cache_bytes,
-                       const std::string& write_policy, bool direct_io) {
+                       const std::string& write_policy, bool direct_io,
+                       int fp8_group_size) {
              EngineConfig cfg;
              cfg.io_threads = io_threads;
              cfg.gpu_blocks_per_file = gpu_blocks_per_file;
@@ -77,8 +78,12 @@ PYBIND11_MODULE(_kvoffload, m) {
                cfg.serialize = Serialize::kRaw;
              else if (serialize == "fp8_e4m3")
                cfg.serialize = Serialize::kFp8E4M3;
+             else if (serialize == "fp8_e4m3_group")
+               cfg.serialize = Serialize::kFp8E4M3Group;
              else
-               throw std::invalid_argument("serialize must be raw|fp8_e4m3");
+               throw std::invalid_argument(
+                   "serialize must be raw|fp8_e4m3|fp8_e4m3_group");
+             cfg.fp8_group_size = fp8_group_size;
              cfg.host_cache_bytes = host_cache_bytes;
              if (write_policy == "through")
                cfg.write_policy = WritePolicy::kThrough;
@@ -105,7 +110,8 @@ PYBIND11_MODULE(_kvoffload, m) {
            py::arg("max_write_queued_seconds") = 30.0, py::arg("gpu_mode") = false,
            py::arg("device") = 0, py::arg("copy_path") = "staged",
            py::arg("serialize") = "raw", py::arg("host_cache_bytes") = 0,
-           py::arg("write_policy") = "through", py::arg("direct_io") = false)
+           py::arg("write_policy") = "through", py::arg("direct_io") = false,
+           py::arg("fp8_group_size") = 128)
       .def(
           "async_store",
           [](StorageOffloadEngine& e,
@@ -212,6 +218,28 @@ PYBIND11_MODULE(_kvoffload, m) {
           },
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
           py::arg("stream") = 0)
+      .def("packed_bytes_fp8_group", &BlockCopier::packed_bytes_fp8_group,
+           py::arg("group"), py::arg("n_blocks"), py::arg("group_size") = 128)
+      .def(
+          "gather_fp8_group",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
+             int group_size, uintptr_t stream) {
+            py::gil_scoped_release rel;
+            c.gather_fp8_group(group, ids, reinterpret_cast<void*>(dst),
+                               group_size, stream);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("dst"),
+          py::arg("group_size") = 128, py::arg("stream") = 0)
+      .def(
+          "scatter_fp8_group",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
+             int group_size, uintptr_t stream) {
+            py::gil_scoped_release rel;
+            c.scatter_fp8_group(group, ids, reinterpret_cast<const void*>(src),
+                                group_size, stream);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("src"),
+          py::arg("group_size") = 128, py::arg("stream") = 0)
       .def(
           "gather",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,

@@ -95,6 +95,59 @@ class BlockCopier {
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
+  // Group-scaled fp8 record size: block_bytes/2 payload + one f32 scale
+  // per group_size elements, per tile.
+  size_t packed_bytes_fp8_group(int group, size_t n_blocks,
+                                int group_size) const {
+    const GroupDesc& g = groups_.at(group);
+    check_group_size(g, group_size);
+    return n_blocks * g.layer_ptrs.size() *
+           StorageOffloadEngine::fp8_group_record_bytes(g.block_bytes,
+                                                        group_size);
+  }
+
+  // Single-pass gather + per-group quantize into dst (device ptr in GPU
+  // mode); needs no scratch. Host mode uses the software twin.
+  void gather_fp8_group(int group, const std::vector<int32_t>& ids, void* dst,
+                        int group_size, uintptr_t stream) {
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_group_size(g, group_size);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp8_group_copy(
+          g, ids, static_cast<uint8_t*>(dst), group_size, /*quantize=*/true);
+      return;
+    }
+    hipError_t err = kvc_launch_gather_fp8_group(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
+        nullptr, static_cast<uint8_t*>(dst),
+        reinterpret_cast<hipStream_t>(stream));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
+  // Dequantize + scatter from a group-scaled fp8 record slab.
+  void scatter_fp8_group(int group, const std::vector<int32_t>& ids,
+                         const void* src, int group_size, uintptr_t stream) {
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_group_size(g, group_size);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp8_group_copy(
+          g, ids, const_cast<uint8_t*>(static_cast<const uint8_t*>(src)),
+          group_size, /*quantize=*/false);
+      return;
+    }
+    hipError_t err = kvc_launch_scatter_fp8_group(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
+        nullptr, static_cast<const uint8_t*>(src),
+        reinterpret_cast<hipStream_t>(stream));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
   // Gather block_ids of `group` into contiguous dst (device ptr in GPU
   // mode). Async on `stream`; caller synchronizes.
   void gather(int group, const std::vector<int32_t>& ids, void* dst,
@@ -139,6 +192,18 @@ class BlockCopier {
         if (id < 0 || id >= g.num_blocks)
           throw std::invalid_argument("block id out of range");
     }
+  }
+
+  static void check_group_size(const GroupDesc& g, int group_size) {
+    if (!fp8_group_size_ok(group_size))
+      throw std::invalid_argument(
+          "fp8 group_size must be 64, 128, 256 or 512 (got " +
+          std::to_string(group_size) + ")");
+    if (g.block_bytes % 16 != 0 || (g.block_bytes / 2) % group_size != 0)
+      throw std::invalid_argument(
+          "block_bytes/2 = " + std::to_string(g.block_bytes / 2) +
+          " elements is not a multiple of fp8 group_size " +
+          std::to_string(group_size));
   }
 
   void host_copy(const GroupDesc& g, const std::vector<int32_t>& ids,

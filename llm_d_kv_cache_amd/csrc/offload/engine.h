@@ -55,6 +55,13 @@ extern "C" hipError_t kvc_launch_scatter_fp8(const void* const*, const uint64_t*
                                              int, uint64_t, const int32_t*, int,
                                              const int32_t*, const uint8_t*,
                                              hipStream_t);
+// group-scaled fp8: the int after block_bytes is the group size in elements
+extern "C" hipError_t kvc_launch_gather_fp8_group(
+    const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
+    int, const int32_t*, uint8_t*, hipStream_t);
+extern "C" hipError_t kvc_launch_scatter_fp8_group(
+    const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
+    int, const int32_t*, const uint8_t*, hipStream_t);
 
 namespace kvo {
 
@@ -77,8 +84,14 @@ enum class CopyPath { kStaged, kZeroCopy, kHostMemcpy };
 
 // Payload serialization: raw bytes, or fp8 e4m3fn quantization of bf16
 // pages (halves wire + storage bytes; one f32 scale per (block, layer)
-// tile appended to each tile record).
-enum class Serialize { kRaw, kFp8E4M3 };
+// tile appended to each tile record). kFp8E4M3Group scales every
+// fp8_group_size-element run on its own (users set it to head_dim): the
+// record is [ n fp8 | n/G f32 scales ], n = block_bytes/2.
+enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group };
+
+inline bool fp8_group_size_ok(int g) {
+  return g == 64 || g == 128 || g == 256 || g == 512;
+}
 
 // Store completion semantics: kThrough = the file rename happened (crash
 // durable); kBack = the slab is resident in the pinned-DRAM tier and the
@@ -104,6 +117,7 @@ struct EngineConfig {
   int device = 0;
   CopyPath copy_path = CopyPath::kStaged;
   Serialize serialize = Serialize::kRaw;
+  int fp8_group_size = 128;  // elements per scale; kFp8E4M3Group only
   // Pinned host-DRAM cache tier (0 = disabled): write-through on store,
   // cache-hit loads skip the filesystem (host_cache.h).
   size_t host_cache_bytes = 0;
@@ -180,10 +194,22 @@ class StorageOffloadEngine {
       cfg_.copy_path = CopyPath::kHostMemcpy;
     }
 
+    const bool grouped = cfg_.serialize == Serialize::kFp8E4M3Group;
+    if (grouped && !fp8_group_size_ok(cfg_.fp8_group_size))
+      throw std::invalid_argument(
+          "fp8_group_size must be 64, 128, 256 or 512 (got " +
+          std::to_string(cfg_.fp8_group_size) + ")");
     size_t max_file_bytes = 0;
-    for (auto& g : groups_) {
+    for (size_t gi = 0; gi < groups_.size(); ++gi) {
+      auto& g = groups_[gi];
       if (g.block_bytes % 16 != 0)
         throw std::invalid_argument("block_bytes must be a multiple of 16");
+      if (grouped && (g.block_bytes / 2) % cfg_.fp8_group_size != 0)
+        throw std::invalid_argument(
+            "group " + std::to_string(gi) + ": block_bytes/2 = " +
+            std::to_string(g.block_bytes / 2) +
+            " elements is not a multiple of fp8_group_size " +
+            std::to_string(cfg_.fp8_group_size));
       if (g.layer_ptrs.size() != g.layer_strides.size())
         throw std::invalid_argument("layer ptr/stride length mismatch");
       max_file_bytes =
@@ -523,8 +549,14 @@ class StorageOffloadEngine {
   }
 
   size_t tile_record_bytes(const GroupDesc& g) const {
-    return cfg_.serialize == Serialize::kFp8E4M3 ? g.block_bytes / 2 + 4
-                                                 : g.block_bytes;
+    switch (cfg_.serialize) {
+      case Serialize::kFp8E4M3:
+        return g.block_bytes / 2 + 4;
+      case Serialize::kFp8E4M3Group:
+        return fp8_group_record_bytes(g.block_bytes, cfg_.fp8_group_size);
+      default:
+        return g.block_bytes;
+    }
   }
 
   size_t file_bytes(const GroupDesc& g, size_t n_blocks) const {
@@ -620,7 +652,15 @@ class StorageOffloadEngine {
                                 : ctx.host_staging->device();
       const int32_t* ids_dev = stage_ids(ctx, ft);
       hipError_t err;
-      if (cfg_.serialize == Serialize::kFp8E4M3) {
+      if (cfg_.serialize == Serialize::kFp8E4M3Group) {
+        // single-pass gather for the staged AND the zero-copy destination:
+        // no scratch, so the tail of the device bounce goes unused
+        err = kvc_launch_gather_fp8_group(
+            const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
+            dev_layer_strides_[ft.group], nl, g.block_bytes,
+            cfg_.fp8_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
+            ctx.stream);
+      } else if (cfg_.serialize == Serialize::kFp8E4M3) {
         if (cfg_.copy_path == CopyPath::kStaged) {
           // split amax+quantize (chip-filling); the partial-max scratch
           // (tiles x slices floats, slices <= 2048/tiles + 1) lives in the
@@ -822,6 +862,32 @@ class StorageOffloadEngine {
     return false;
   }
 
+  // Scatter (raw), or dequantize+scatter (either fp8 mode), of the packed
+  // records at `src` into the pages of ft.block_ids.
+  hipError_t launch_scatter(WorkerCtx& ctx, const FileTransfer& ft,
+                            const int32_t* ids_dev, const uint8_t* src) {
+    const GroupDesc& g = groups_[ft.group];
+    const int nb = static_cast<int>(ft.block_ids.size());
+    const int nl = static_cast<int>(g.layer_ptrs.size());
+    const void* const* ptrs =
+        const_cast<const void* const*>(dev_layer_ptrs_[ft.group]);
+    const uint64_t* strides = dev_layer_strides_[ft.group];
+    switch (cfg_.serialize) {
+      case Serialize::kFp8E4M3Group:
+        return kvc_launch_scatter_fp8_group(
+            ptrs, strides, nl, g.block_bytes, cfg_.fp8_group_size,
+            ft.block_ids.data(), nb, ids_dev, src, ctx.stream);
+      case Serialize::kFp8E4M3:
+        return kvc_launch_scatter_fp8(ptrs, strides, nl, g.block_bytes,
+                                      ft.block_ids.data(), nb, ids_dev, src,
+                                      ctx.stream);
+      default:
+        return kvc_launch_scatter(ptrs, strides, nl, g.block_bytes,
+                                  ft.block_ids.data(), nb, ids_dev, src,
+                                  ctx.stream);
+    }
+  }
+
   void load_one(WorkerCtx& ctx, const FileTransfer& ft) {
     const GroupDesc& g = groups_[ft.group];
     const int nb = static_cast<int>(ft.block_ids.size());
@@ -900,17 +966,7 @@ class StorageOffloadEngine {
       touch_atime(ft.path);
       const int32_t* ids_dev = stage_ids(ctx, ft);
       hipError_t err =
-          cfg_.serialize == Serialize::kFp8E4M3
-              ? kvc_launch_scatter_fp8(
-                    const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
-                    dev_layer_strides_[ft.group], nl, g.block_bytes,
-                    ft.block_ids.data(), nb, ids_dev,
-                    ctx.device_staging->ptr(), ctx.stream)
-              : kvc_launch_scatter(
-                    const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
-                    dev_layer_strides_[ft.group], nl, g.block_bytes,
-                    ft.block_ids.data(), nb, ids_dev,
-                    ctx.device_staging->ptr(), ctx.stream);
+          launch_scatter(ctx, ft, ids_dev, ctx.device_staging->ptr());
       if (err != hipSuccess) throw HipError(hipGetErrorString(err));
       double s0 = now_s();
       KVO_HIP_CHECK(hipStreamSynchronize(ctx.stream));
@@ -956,16 +1012,7 @@ class StorageOffloadEngine {
       double t2 = now_s();
       stats_inc([&](EngineStats& s) { s.t_h2d_ms += (t2 - t1) * 1e3; });
       const int32_t* ids_dev = stage_ids(ctx, ft);
-      hipError_t err =
-          cfg_.serialize == Serialize::kFp8E4M3
-              ? kvc_launch_scatter_fp8(
-                    const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
-                    dev_layer_strides_[ft.group], nl, g.block_bytes,
-                    ft.block_ids.data(), nb, ids_dev, kernel_src, ctx.stream)
-              : kvc_launch_scatter(
-                    const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
-                    dev_layer_strides_[ft.group], nl, g.block_bytes,
-                    ft.block_ids.data(), nb, ids_dev, kernel_src, ctx.stream);
+      hipError_t err = launch_scatter(ctx, ft, ids_dev, kernel_src);
       if (err != hipSuccess) throw HipError(hipGetErrorString(err));
       KVO_HIP_CHECK(hipStreamSynchronize(ctx.stream));
       double t3 = now_s();
@@ -988,6 +1035,8 @@ class StorageOffloadEngine {
         uint8_t* out = dst + (bi * nl + l) * rec;
         if (cfg_.serialize == Serialize::kFp8E4M3)
           fp8_quantize_tile(src, g.block_bytes, out);
+        else if (cfg_.serialize == Serialize::kFp8E4M3Group)
+          fp8_group_quantize_tile(src, g.block_bytes, cfg_.fp8_group_size, out);
         else
           std::memcpy(out, src, g.block_bytes);
       }
@@ -1005,6 +1054,8 @@ class StorageOffloadEngine {
         const uint8_t* in = src + (bi * nl + l) * rec;
         if (cfg_.serialize == Serialize::kFp8E4M3)
           fp8_dequantize_tile(in, g.block_bytes, dst);
+        else if (cfg_.serialize == Serialize::kFp8E4M3Group)
+          fp8_group_dequantize_tile(in, g.block_bytes, cfg_.fp8_group_size, dst);
         else
           std::memcpy(dst, in, g.block_bytes);
       }
@@ -1056,6 +1107,28 @@ class StorageOffloadEngine {
     }
     return sign | static_cast<uint8_t>((exp_field << 3) | m);
   }
+  // Round-to-nearest-even e4m3fn encoder of the group-scaled mode (the
+  // CDNA4 cvt_pk_fp8_f32 rounding; f32_to_fp8 above rounds ties upward
+  // and stays as the per-tile mode's codec). Finite inputs only; the sign
+  // survives a magnitude that rounds to zero.
+  static uint8_t f32_to_fp8_rne(float x) {
+    uint32_t w;
+    std::memcpy(&w, &x, 4);
+    const uint8_t sign = static_cast<uint8_t>((w >> 24) & 0x80);
+    w &= 0x7fffffffu;
+    float a;
+    std::memcpy(&a, &w, 4);
+    if (a < 0.015625f) {
+      // below the min normal 2^-6: code = RNE(a / 2^-9) in [0, 8]; 8 is
+      // the encoding of 2^-6 itself. a * 512 is exact.
+      return sign | static_cast<uint8_t>(std::nearbyint(a * 512.0f));
+    }
+    // f32 bits >> 20 = (exponent << 3) | top-3 mantissa bits; rounding the
+    // dropped 20 bits to even carries into the exponent by itself
+    w += 0x7ffffu + ((w >> 20) & 1);
+    const uint32_t code = (w >> 20) - ((127u - 7u) << 3);
+    return sign | static_cast<uint8_t>(code > 0x7e ? 0x7e : code);
+  }
   static float fp8_to_f32(uint8_t b) {
     uint8_t sign = b & 0x80;
     int exp_field = (b >> 3) & 0xf;
@@ -1088,7 +1161,67 @@ class StorageOffloadEngine {
     }
   }
 
+  static size_t fp8_group_record_bytes(uint64_t block_bytes, int group_size) {
+    const size_t n = block_bytes / 2;
+    return n + 4 * (n / static_cast<size_t>(group_size));
+  }
+
+  // Software twin of kvc_gather_fp8_group / kvc_scatter_fp8_group (engine
+  // host mode and BlockCopier's CPU path): same bytes as the kernels.
+  static void host_fp8_group_copy(const GroupDesc& g,
+                                  const std::vector<int32_t>& ids,
+                                  uint8_t* packed, int group_size,
+                                  bool quantize) {
+    const size_t nl = g.layer_ptrs.size();
+    const size_t rec = fp8_group_record_bytes(g.block_bytes, group_size);
+    for (size_t bi = 0; bi < ids.size(); ++bi) {
+      for (size_t l = 0; l < nl; ++l) {
+        uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +
+                        static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
+        uint8_t* slab = packed + (bi * nl + l) * rec;
+        if (quantize)
+          fp8_group_quantize_tile(page, g.block_bytes, group_size, slab);
+        else
+          fp8_group_dequantize_tile(slab, g.block_bytes, group_size, page);
+      }
+    }
+  }
+
   private:
+  // Record starts are only 4-byte aligned and scales follow n payload
+  // bytes: scales move through memcpy.
+  static void fp8_group_quantize_tile(const uint8_t* src, size_t block_bytes,
+                                      int group_size, uint8_t* out) {
+    const size_t n = block_bytes / 2;
+    const size_t G = static_cast<size_t>(group_size);
+    const uint16_t* in = reinterpret_cast<const uint16_t*>(src);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      const uint16_t* x = in + gi * G;
+      float amax = 0.0f;
+      for (size_t i = 0; i < G; ++i)
+        amax = std::max(amax, std::abs(bf16_to_f32(x[i])));
+      if (amax <= 0.0f) amax = 1.0f;
+      const float scale = amax / 448.0f;
+      const float inv = 448.0f / amax;
+      for (size_t i = 0; i < G; ++i)
+        out[gi * G + i] = f32_to_fp8_rne(bf16_to_f32(x[i]) * inv);
+      std::memcpy(out + n + 4 * gi, &scale, 4);
+    }
+  }
+
+  static void fp8_group_dequantize_tile(const uint8_t* in, size_t block_bytes,
+                                        int group_size, uint8_t* dst) {
+    const size_t n = block_bytes / 2;
+    const size_t G = static_cast<size_t>(group_size);
+    uint16_t* out = reinterpret_cast<uint16_t*>(dst);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      float scale;
+      std::memcpy(&scale, in + n + 4 * gi, 4);
+      for (size_t i = 0; i < G; ++i)
+        out[gi * G + i] = f32_to_bf16(fp8_to_f32(in[gi * G + i]) * scale);
+    }
+  }
+
   static void fp8_quantize_tile(const uint8_t* src, size_t block_bytes,
                          uint8_t* out) {
     const size_t n = block_bytes / 2;

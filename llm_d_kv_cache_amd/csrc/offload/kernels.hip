@@ -510,4 +510,192 @@ extern "C" hipError_t kvc_launch_scatter_fp8(
   return hipGetLastError();
 }
 
+// ---- group-scaled fp8 (one f32 scale per G-element run) ---------------------
+// serialize="fp8_e4m3_group": a tile record is
+//   [ n fp8 bytes | n/G f32 scales ],  n = block_bytes/2,  n % G == 0
+// with G in {64, 128, 256, 512}. At 8 bf16 per lane a group is G/8 = 8..64
+// consecutive lanes of one wave, so the group amax is a log2(G/8)-step xor
+// butterfly inside the wave: ONE pass over the source, no scratch slab, no
+// LDS, no second launch — which also makes it the right kernel for the
+// zero-copy path (nothing but the record itself crosses PCIe).
+//
+// Per group, all f32: amax = max|x| (0 -> 1), scale = amax/448 (stored),
+// q = RNE_e4m3fn(x * (448/amax)); load: y = bf16_RNE(f32(q) * scale).
+
+// kLanes = G/8 lanes per group. The grid-stride loop runs on a WAVE-UNIFORM
+// base with a guarded body, so every lane of the wave reaches every shuffle
+// even when n/8 is not a multiple of 64; groups are kLanes-aligned runs of
+// v and n % G == 0, so a group is either wholly inside the tile or wholly
+// past its end, and the xor butterfly (offsets < kLanes) never leaves it.
+template <int kLanes>
+__global__ __launch_bounds__(256) void kvc_gather_fp8_group(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst) {
+  static_assert(kLanes == 8 || kLanes == 16 || kLanes == 32 || kLanes == 64,
+                "group must span 8..64 lanes of one wave");
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes / 2;
+  const uint64_t n_groups = n_elems / (8 * kLanes);
+  const uint64_t record = n_elems + 4 * n_groups;
+  const uint4* __restrict__ vsrc = reinterpret_cast<const uint4*>(
+      static_cast<const uint8_t*>(layer_ptrs[l]) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  uint8_t* __restrict__ payload = dst + static_cast<uint64_t>(tile) * record;
+  uint2* __restrict__ vout = reinterpret_cast<uint2*>(payload);
+  float* __restrict__ scales = reinterpret_cast<float*>(payload + n_elems);
+  const uint64_t nvec = n_elems / 8;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t vb = static_cast<uint64_t>(blockIdx.y) * blockDim.x +
+                     (threadIdx.x & ~63u);
+       vb < nvec; vb += stride) {
+    const uint64_t v = vb + lane;
+    const bool live = v < nvec;
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (live) w = vsrc[v];
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
+    float x[8];
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[2 * j] = bf16_to_f32(static_cast<uint16_t>(dw[j]));
+      x[2 * j + 1] = bf16_to_f32(static_cast<uint16_t>(dw[j] >> 16));
+      amax = fmaxf(amax, fmaxf(fabsf(x[2 * j]), fabsf(x[2 * j + 1])));
+    }
+#pragma unroll
+    for (int off = kLanes / 2; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    if (amax <= 0.0f) amax = 1.0f;
+    const float inv_scale = kFp8Max / amax;
+    uint2 out;
+    uint32_t lo = 0, hi = 0;
+    // word_sel must be an immediate: unrolled by hand
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv_scale, x[1] * inv_scale, lo, 0);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv_scale, x[3] * inv_scale, lo, 1);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4] * inv_scale, x[5] * inv_scale, hi, 0);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv_scale, x[7] * inv_scale, hi, 1);
+    out.x = lo;
+    out.y = hi;
+    if (live) {
+      vout[v] = out;
+      if ((lane & (kLanes - 1)) == 0) scales[v / kLanes] = amax / kFp8Max;
+    }
+  }
+}
+
+// Sliced dequantize+scatter for group-scaled records: same shape as
+// kvc_scatter_fp8, but the scale is scales[(8 v) / G] = scales[v >> lane_shift]
+// (lane_shift = log2(G/8)) — one address per G/8-lane run, an L2-hit load.
+__global__ __launch_bounds__(256) void kvc_scatter_fp8_group(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, int lane_shift, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src) {
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes / 2;
+  const uint64_t nvec = n_elems / 8;
+  const uint64_t record = n_elems + 4 * (nvec >> lane_shift);
+  uint4* __restrict__ vout = reinterpret_cast<uint4*>(
+      static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  const uint8_t* __restrict__ payload =
+      src + static_cast<uint64_t>(tile) * record;
+  const uint2* __restrict__ vin = reinterpret_cast<const uint2*>(payload);
+  const float* __restrict__ scales =
+      reinterpret_cast<const float*>(payload + n_elems);
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  for (uint64_t v = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
+       v < nvec; v += stride) {
+    const float scale = scales[v >> lane_shift];
+    uint2 w = vin[v];
+    uint4 o;
+    uint32_t* od = reinterpret_cast<uint32_t*>(&o);
+    const uint32_t words[2] = {w.x, w.y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint8_t b0 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16));
+      uint8_t b1 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16 + 8));
+      uint16_t h0 = f32_to_bf16(fp8_e4m3_to_f32(b0) * scale);
+      uint16_t h1 = f32_to_bf16(fp8_e4m3_to_f32(b1) * scale);
+      od[j] = static_cast<uint32_t>(h0) | (static_cast<uint32_t>(h1) << 16);
+    }
+    vout[v] = o;
+  }
+}
+
+namespace {
+
+// G -> log2(G/8); -1 for anything but 64/128/256/512 or a tile the group
+// size does not divide.
+inline int fp8_group_lane_shift(uint64_t block_bytes, int group_size) {
+  int shift;
+  switch (group_size) {
+    case 64: shift = 3; break;
+    case 128: shift = 4; break;
+    case 256: shift = 5; break;
+    case 512: shift = 6; break;
+    default: return -1;
+  }
+  if (block_bytes % 16 != 0 ||
+      (block_bytes / 2) % static_cast<uint64_t>(group_size) != 0)
+    return -1;
+  return shift;
+}
+
+}  // namespace
+
+extern "C" hipError_t kvc_launch_gather_fp8_group(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, int group_size,
+    const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
+    uint8_t* dst, hipStream_t stream) {
+  const int shift = fp8_group_lane_shift(block_bytes, group_size);
+  if (shift < 0) return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = copy_grid(tiles, block_bytes);
+#define KVC_GATHER_GROUP(LANES)                                               \
+  hipLaunchKernelGGL(kvc_gather_fp8_group<LANES>, grid, dim3(256), 0, stream, \
+                     layer_ptrs_dev, layer_strides_dev, num_layers,           \
+                     block_bytes, bl, ids_dev, dst)
+  switch (shift) {
+    case 3: KVC_GATHER_GROUP(8); break;
+    case 4: KVC_GATHER_GROUP(16); break;
+    case 5: KVC_GATHER_GROUP(32); break;
+    default: KVC_GATHER_GROUP(64); break;
+  }
+#undef KVC_GATHER_GROUP
+  return hipGetLastError();
+}
+
+extern "C" hipError_t kvc_launch_scatter_fp8_group(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, int group_size,
+    const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
+    const uint8_t* src, hipStream_t stream) {
+  const int shift = fp8_group_lane_shift(block_bytes, group_size);
+  if (shift < 0) return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = copy_grid(tiles, block_bytes);
+  hipLaunchKernelGGL(kvc_scatter_fp8_group, grid, dim3(256), 0, stream,
+                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
+                     shift, bl, ids_dev, src);
+  return hipGetLastError();
+}
+
 }  // namespace kvo

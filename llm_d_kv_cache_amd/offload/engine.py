@@ -21,12 +21,50 @@ class OffloadEngineConfig:
     read_preferring_ratio: float = 0.75
     max_write_queued_seconds: float = 30.0
     copy_path: str = "staged"  # staged | zero_copy | host
-    serialize: str = "raw"     # raw | fp8_e4m3 (bf16 pages -> fp8 + scale)
+    # raw | fp8_e4m3 (bf16 pages -> fp8 + one scale per (block, layer) tile)
+    # | fp8_e4m3_group (fp8 + one scale per fp8_group_size elements)
+    serialize: str = "raw"
+    # elements per scale for fp8_e4m3_group (set it to head_dim); one of
+    # 64/128/256/512, ignored by the other modes
+    fp8_group_size: int = 128
     host_cache_bytes: int = 0  # pinned-DRAM cache tier (0 = off)
     write_policy: str = "through"  # through | back (flush async via DRAM tier)
     direct_io: bool = False    # O_DIRECT for NVMe (auto-fallback elsewhere)
     device: int = 0
     staging_budget_bytes: int = DEFAULT_STAGING_BUDGET_BYTES
+
+
+SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group")
+FP8_GROUP_SIZES = (64, 128, 256, 512)
+
+
+def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
+                      group: int = 0) -> int:
+    """Bytes one (block, layer) tile occupies in a file/object/slab.
+
+    raw: block_bytes. fp8_e4m3: n + 4 (n = block_bytes/2 fp8 bytes, one f32
+    scale). fp8_e4m3_group: n + 4*n/G (one f32 scale per G elements).
+    Raises ValueError for an unknown mode, a group size outside
+    FP8_GROUP_SIZES, or a KV group whose tile G does not divide.
+    """
+    if serialize == "raw":
+        return block_bytes
+    if serialize == "fp8_e4m3":
+        return block_bytes // 2 + 4
+    if serialize != "fp8_e4m3_group":
+        raise ValueError(
+            f"serialize must be one of {'|'.join(SERIALIZE_MODES)}, "
+            f"got {serialize!r}")
+    if fp8_group_size not in FP8_GROUP_SIZES:
+        raise ValueError(
+            f"fp8_group_size must be one of {FP8_GROUP_SIZES}, "
+            f"got {fp8_group_size}")
+    n = block_bytes // 2
+    if block_bytes % 16 != 0 or n % fp8_group_size != 0:
+        raise ValueError(
+            f"KV group {group}: block_bytes={block_bytes} holds {n} bf16 "
+            f"elements, not a multiple of fp8_group_size={fp8_group_size}")
+    return n + 4 * (n // fp8_group_size)
 
 
 class TorchOffloadEngine:
@@ -65,7 +103,7 @@ class TorchOffloadEngine:
         native_groups = []
         self.group_geometry: List[dict] = []
         max_file_bytes = 0
-        for g in groups:
+        for gi, g in enumerate(groups):
             ptrs = [t.data_ptr() for t in g]
             strides = [t.stride(0) * t.element_size() for t in g]
             block_bytes = {t.stride(0) * t.element_size() for t in g}
@@ -75,7 +113,12 @@ class TorchOffloadEngine:
             # the actual payload per block may be smaller than the stride;
             # canonical layouts are dense so stride == payload
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
-            record_bytes = bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb
+            if config.serialize == "fp8_e4m3_group":
+                record_bytes = tile_record_bytes(
+                    config.serialize, bb, config.fp8_group_size, gi)
+            else:
+                record_bytes = (bb // 2 + 4 if config.serialize == "fp8_e4m3"
+                                else bb)
             self.group_geometry.append(
                 {
                     "num_layers": len(g),
@@ -113,6 +156,7 @@ class TorchOffloadEngine:
             host_cache_bytes=config.host_cache_bytes,
             write_policy=config.write_policy,
             direct_io=config.direct_io,
+            fp8_group_size=config.fp8_group_size,
         )
         del stream
         # keep tensor refs: the native engine holds raw pointers
@@ -174,7 +218,8 @@ class TorchOffloadEngine:
         (peer/DRAM-tier bridge). Returns a host uint8 tensor of exactly the
         first n_blocks' packed bytes, or None on a cache miss / short
         entry. The payload layout matches the file layout (raw gather
-        layout, or fp8 tile records when serialize="fp8_e4m3")."""
+        layout, per-tile fp8 records when serialize="fp8_e4m3", group-scaled
+        fp8 records when serialize="fp8_e4m3_group")."""
         import torch
 
         geo = self.group_geometry[group]

@@ -30,7 +30,9 @@ class ObjStorageConfig:
     bucket: str = "kvcache"
     io_threads: int = 8
     timeout_s: float = 30.0
-    serialize: str = "raw"  # raw | fp8_e4m3 (via the native codec kernels)
+    # raw | fp8_e4m3 | fp8_e4m3_group (via the native codec kernels)
+    serialize: str = "raw"
+    fp8_group_size: int = 128  # elements per scale, fp8_e4m3_group only
     # AWS SigV4 credentials; leave access_key empty for anonymous access.
     access_key: str = ""
     secret_key: str = ""
@@ -157,6 +159,7 @@ class ObjStorageEngine:
         import torch
 
         from .. import ensure_offload_native
+        from .engine import tile_record_bytes
 
         ko = ensure_offload_native()
         self._torch = torch
@@ -164,12 +167,18 @@ class ObjStorageEngine:
         self.gpu_mode = groups[0][0].is_cuda
         native_groups = []
         self.group_geometry: List[dict] = []
-        for g in groups:
+        self._fp8_group = config.serialize == "fp8_e4m3_group"
+        self._group_size = config.fp8_group_size
+        for gi, g in enumerate(groups):
             ptrs = [t.data_ptr() for t in g]
             strides = [t.stride(0) * t.element_size() for t in g]
             bb = strides[0]
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
-            record = bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb
+            if self._fp8_group:
+                record = tile_record_bytes(config.serialize, bb,
+                                           config.fp8_group_size, gi)
+            else:
+                record = bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb
             self.group_geometry.append(
                 {"num_layers": len(g), "block_bytes": bb, "record_bytes": record,
                  "num_device_blocks": g[0].shape[0]}
@@ -190,6 +199,9 @@ class ObjStorageEngine:
     # ---- engine surface -----------------------------------------------------
 
     def _packed(self, group: int, n_blocks: int) -> int:
+        if self._fp8_group:
+            return self._copier.packed_bytes_fp8_group(group, n_blocks,
+                                                       self._group_size)
         if self._fp8:
             return self._copier.packed_bytes_fp8(group, n_blocks)
         return self._copier.packed_bytes(group, n_blocks)
@@ -211,7 +223,11 @@ class ObjStorageEngine:
                                     device="cuda")
             stream = self._torch.cuda.Stream()
             with self._torch.cuda.stream(stream):
-                if self._fp8:
+                if self._fp8_group:
+                    self._copier.gather_fp8_group(group, ids, dev.data_ptr(),
+                                                  self._group_size,
+                                                  stream.cuda_stream)
+                elif self._fp8:
                     self._copier.gather_fp8(group, ids, dev.data_ptr(),
                                             dev.data_ptr() + nb,
                                             stream.cuda_stream)
@@ -223,7 +239,10 @@ class ObjStorageEngine:
             stream.synchronize()
         else:
             host = self._slab(group, len(ids))
-            if self._fp8:
+            if self._fp8_group:
+                self._copier.gather_fp8_group(group, ids, host.data_ptr(),
+                                              self._group_size, 0)
+            elif self._fp8:
                 self._copier.gather_fp8(group, ids, host.data_ptr(), 0, 0)
             else:
                 self._copier.gather(group, ids, host.data_ptr(), 0)
@@ -238,8 +257,14 @@ class ObjStorageEngine:
         if len(data) != len(ids) * rec:
             raise IOError(f"short object read for {key}")
         host = self._torch.frombuffer(bytearray(data), dtype=self._torch.uint8)
-        scatter = (self._copier.scatter_fp8 if self._fp8
-                   else self._copier.scatter)
+        if self._fp8_group:
+            def scatter(group, ids, src, stream):
+                self._copier.scatter_fp8_group(group, ids, src,
+                                               self._group_size, stream)
+        elif self._fp8:
+            scatter = self._copier.scatter_fp8
+        else:
+            scatter = self._copier.scatter
         if self.gpu_mode:
             dev = host.cuda()
             self._torch.cuda.synchronize()

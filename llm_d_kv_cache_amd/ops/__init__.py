@@ -9,6 +9,11 @@ built from, for embedding in other MI355X services.
   the copier (gather_fp8 / scatter_fp8 with packed_bytes_fp8 /
   fp8_scratch_bytes sizing); the offload engine's serialize="fp8_e4m3"
   rides the same kernels.
+- group-scaled fp8: gather_fp8_group / scatter_fp8_group (sized by
+  packed_bytes_fp8_group) keep one f32 scale per group_size elements
+  (64/128/256/512; set it to head_dim) instead of one per tile. The gather
+  is a single pass — the group amax is an in-wave butterfly — and needs no
+  scratch. serialize="fp8_e4m3_group" rides these kernels.
 """
 from __future__ import annotations
 

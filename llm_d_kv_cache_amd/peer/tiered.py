@@ -24,7 +24,25 @@ def make_dram_lookup(engine, mapper):
     """Build a PeerMigrationService dram_lookup callback from an offload
     engine + file mapper: serves PULL requests out of the pinned host-DRAM
     cache when the blocks are no longer registered in HBM. Returns
-    (host_tensor, is_fp8) or None."""
+    (host_tensor, is_fp8) or None.
+
+    The peer wire carries raw slabs or per-tile fp8 records only. An engine
+    with serialize="fp8_e4m3_group" keeps group-scaled records in its DRAM
+    tier, which the wire cannot label, so its lookup reports a miss every
+    time (logged once) and pulls fall through to the storage tier."""
+    if engine.config.serialize == "fp8_e4m3_group":
+        warned = []
+
+        def never(chunk_hash, group, n_blocks):
+            if not warned:
+                warned.append(True)
+                log.warning(
+                    "DRAM-tier peer serving is off for serialize="
+                    "'fp8_e4m3_group': the peer wire has no group-scaled "
+                    "fp8 format; pulls fall through to storage")
+            return None
+
+        return never
     fp8 = engine.config.serialize == "fp8_e4m3"
 
     def lookup(chunk_hash, group, n_blocks):
