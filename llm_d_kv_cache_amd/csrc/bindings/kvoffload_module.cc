@@ -33,6 +33,7 @@ PYBIND11_MODULE(_kvoffload, m) {
       .def_readonly("host_cache_stores", &EngineStats::host_cache_stores)
       .def_readonly("writeback_flushes", &EngineStats::writeback_flushes)
       .def_readonly("errors", &EngineStats::errors)
+      .def_readonly("checksum_failures", &EngineStats::checksum_failures)
       .def_readonly("avg_write_seconds", &EngineStats::avg_write_seconds)
       .def_readonly("bytes_stored", &EngineStats::bytes_stored)
       .def_readonly("bytes_loaded", &EngineStats::bytes_loaded)
@@ -57,8 +58,9 @@ PYBIND11_MODULE(_kvoffload, m) {
                        bool gpu_mode, int device, const std::string& copy_path,
                        const std::string& serialize, size_t host_cache_bytes,
                        const std::string& write_policy, bool direct_io,
-                       int fp8_group_size) {
+                       int fp8_group_size, bool checksum) {
              EngineConfig cfg;
+             cfg.checksum = checksum;
              cfg.io_threads = io_threads;
              cfg.gpu_blocks_per_file = gpu_blocks_per_file;
              cfg.read_preferring_ratio = read_preferring_ratio;
@@ -111,7 +113,7 @@ PYBIND11_MODULE(_kvoffload, m) {
            py::arg("device") = 0, py::arg("copy_path") = "staged",
            py::arg("serialize") = "raw", py::arg("host_cache_bytes") = 0,
            py::arg("write_policy") = "through", py::arg("direct_io") = false,
-           py::arg("fp8_group_size") = 128)
+           py::arg("fp8_group_size") = 128, py::arg("checksum") = false)
       .def(
           "async_store",
           [](StorageOffloadEngine& e,
@@ -193,71 +195,120 @@ PYBIND11_MODULE(_kvoffload, m) {
            }),
            py::arg("groups"), py::arg("gpu_mode") = false, py::arg("device") = 0)
       .def("packed_bytes", &BlockCopier::packed_bytes, py::arg("group"),
-           py::arg("n_blocks"))
+           py::arg("n_blocks"), py::arg("checksum") = false)
       .def("packed_bytes_fp8", &BlockCopier::packed_bytes_fp8, py::arg("group"),
-           py::arg("n_blocks"))
+           py::arg("n_blocks"), py::arg("checksum") = false)
+      .def(
+          "seal_records",
+          [](BlockCopier& c, uintptr_t ptr, size_t tiles, size_t payload_bytes,
+             uintptr_t stream) {
+            py::gil_scoped_release rel;
+            c.seal_records(reinterpret_cast<void*>(ptr), tiles, payload_bytes,
+                           stream);
+          },
+          py::arg("ptr"), py::arg("tiles"), py::arg("payload_bytes"),
+          py::arg("stream") = 0,
+          "Fill the 16-byte checksum footer of every record of a slab")
+      .def(
+          "verify_records",
+          [](BlockCopier& c, uintptr_t ptr, size_t tiles, size_t payload_bytes,
+             uintptr_t stream) {
+            std::pair<int64_t, int64_t> r;
+            {
+              py::gil_scoped_release rel;
+              r = c.verify_records(reinterpret_cast<const void*>(ptr), tiles,
+                                   payload_bytes, stream);
+            }
+            return py::make_tuple(r.first, r.second);
+          },
+          py::arg("ptr"), py::arg("tiles"), py::arg("payload_bytes"),
+          py::arg("stream") = 0,
+          "Check every footer: (bad records, first bad index or -1)")
       .def("fp8_scratch_bytes", &BlockCopier::fp8_scratch_bytes,
            py::arg("group"), py::arg("n_blocks"))
       .def(
           "gather_fp8",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
-             uintptr_t scratch, uintptr_t stream) {
+             uintptr_t scratch, uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
             c.gather_fp8(group, ids, reinterpret_cast<void*>(dst),
-                         reinterpret_cast<void*>(scratch), stream);
+                         reinterpret_cast<void*>(scratch), stream, checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("dst"),
-          py::arg("scratch") = 0, py::arg("stream") = 0)
+          py::arg("scratch") = 0, py::arg("stream") = 0,
+          py::arg("checksum") = false)
       .def(
           "scatter_fp8",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
-             uintptr_t stream) {
+             uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
             c.scatter_fp8(group, ids, reinterpret_cast<const void*>(src),
-                          stream);
+                          stream, checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
-          py::arg("stream") = 0)
+          py::arg("stream") = 0, py::arg("checksum") = false)
       .def("packed_bytes_fp8_group", &BlockCopier::packed_bytes_fp8_group,
-           py::arg("group"), py::arg("n_blocks"), py::arg("group_size") = 128)
+           py::arg("group"), py::arg("n_blocks"), py::arg("group_size") = 128,
+           py::arg("checksum") = false)
       .def(
           "gather_fp8_group",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
-             int group_size, uintptr_t stream) {
+             int group_size, uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
             c.gather_fp8_group(group, ids, reinterpret_cast<void*>(dst),
-                               group_size, stream);
+                               group_size, stream, checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("dst"),
-          py::arg("group_size") = 128, py::arg("stream") = 0)
+          py::arg("group_size") = 128, py::arg("stream") = 0,
+          py::arg("checksum") = false)
       .def(
           "scatter_fp8_group",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
-             int group_size, uintptr_t stream) {
+             int group_size, uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
             c.scatter_fp8_group(group, ids, reinterpret_cast<const void*>(src),
-                                group_size, stream);
+                                group_size, stream, checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
-          py::arg("group_size") = 128, py::arg("stream") = 0)
+          py::arg("group_size") = 128, py::arg("stream") = 0,
+          py::arg("checksum") = false)
       .def(
           "gather",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
-             uintptr_t stream) {
+             uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
-            c.gather(group, ids, reinterpret_cast<void*>(dst), stream);
+            c.gather(group, ids, reinterpret_cast<void*>(dst), stream, checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("dst"),
-          py::arg("stream") = 0)
+          py::arg("stream") = 0, py::arg("checksum") = false)
       .def(
           "scatter",
           [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
-             uintptr_t stream) {
+             uintptr_t stream, bool checksum) {
             py::gil_scoped_release rel;
-            c.scatter(group, ids, reinterpret_cast<const void*>(src), stream);
+            c.scatter(group, ids, reinterpret_cast<const void*>(src), stream,
+                      checksum);
           },
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
-          py::arg("stream") = 0);
+          py::arg("stream") = 0, py::arg("checksum") = false);
+
+  m.def(
+      "record_checksum",
+      [](py::buffer buf) {
+        py::buffer_info info = buf.request();
+        const size_t n = static_cast<size_t>(info.size) *
+                         static_cast<size_t>(info.itemsize);
+        if (n % 4 != 0)
+          throw std::invalid_argument(
+              "record_checksum: payload length must be a multiple of 4");
+        if (!PyBuffer_IsContiguous(info.view(), 'C'))
+          throw std::invalid_argument(
+              "record_checksum: buffer must be C-contiguous");
+        return record_checksum(static_cast<const uint8_t*>(info.ptr), n);
+      },
+      py::arg("buffer"),
+      "sum field of a record's checksum footer over the payload bytes (host "
+      "twin of the seal/verify kernels)");
 
   m.def(
       "prefix_hash",

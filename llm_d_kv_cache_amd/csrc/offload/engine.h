@@ -28,6 +28,7 @@
 #include <map>
 #include <unordered_map>
 
+#include "checksum.h"
 #include "common.h"
 #include "file_io.h"
 #include "host_cache.h"
@@ -36,32 +37,44 @@
 
 // Launchers take host block ids (by-value kernarg, <=128) OR a device
 // pointer (ids_dev != nullptr) for bigger transfers — no kernel-side
-// blocks-per-file ceiling.
+// blocks-per-file ceiling. The trailing uint32_t is the footer bytes every
+// record carries behind its payload: 0 (dense layout) or 16 (checksums).
 extern "C" hipError_t kvc_launch_gather(const void* const*, const uint64_t*, int,
                                         uint64_t, const int32_t*, int,
-                                        const int32_t*, uint8_t*, hipStream_t);
+                                        const int32_t*, uint8_t*, hipStream_t,
+                                        uint32_t);
 extern "C" hipError_t kvc_launch_scatter(const void* const*, const uint64_t*, int,
                                          uint64_t, const int32_t*, int,
                                          const int32_t*, const uint8_t*,
-                                         hipStream_t);
+                                         hipStream_t, uint32_t);
 extern "C" hipError_t kvc_launch_gather_fp8(const void* const*, const uint64_t*,
                                             int, uint64_t, const int32_t*, int,
                                             const int32_t*, uint8_t*,
-                                            hipStream_t);
+                                            hipStream_t, uint32_t);
 extern "C" hipError_t kvc_launch_gather_fp8_split(
     const void* const*, const uint64_t*, int, uint64_t, const int32_t*, int,
-    const int32_t*, uint8_t*, float*, hipStream_t);
+    const int32_t*, uint8_t*, float*, hipStream_t, uint32_t);
 extern "C" hipError_t kvc_launch_scatter_fp8(const void* const*, const uint64_t*,
                                              int, uint64_t, const int32_t*, int,
                                              const int32_t*, const uint8_t*,
-                                             hipStream_t);
+                                             hipStream_t, uint32_t);
 // group-scaled fp8: the int after block_bytes is the group size in elements
 extern "C" hipError_t kvc_launch_gather_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
-    int, const int32_t*, uint8_t*, hipStream_t);
+    int, const int32_t*, uint8_t*, hipStream_t, uint32_t);
 extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
-    int, const int32_t*, const uint8_t*, hipStream_t);
+    int, const int32_t*, const uint8_t*, hipStream_t, uint32_t);
+// Record checksums (checksum.h has the format and the host twin). slab holds
+// `tiles` records of payload_bytes + 16; scratch is
+// kvc_checksum_scratch_bytes(tiles) of 8-byte aligned device memory; result
+// is two device-writable u32 (bad count, first bad index).
+extern "C" size_t kvc_checksum_scratch_bytes(size_t tiles);
+extern "C" hipError_t kvc_launch_seal_records(uint8_t*, uint32_t, uint64_t,
+                                              uint64_t*, hipStream_t);
+extern "C" hipError_t kvc_launch_verify_records(const uint8_t*, uint32_t,
+                                                uint64_t, uint64_t*, uint32_t*,
+                                                hipStream_t);
 
 namespace kvo {
 
@@ -126,6 +139,11 @@ struct EngineConfig {
   // unsupported filesystems/unaligned transfers) — the GDS-substitute
   // mode (no cuFile exists on ROCm; see docs/architecture.md).
   bool direct_io = false;
+  // Per-record checksums: every tile record gains a 16-byte footer
+  // (checksum.h) that is sealed on store and verified on load before any KV
+  // page is written. Files with and without footers must not share a
+  // directory: tag the FileMapper dtype with "+ck" (docs/configuration.md).
+  bool checksum = false;
 };
 
 struct FileTransfer {
@@ -156,6 +174,7 @@ struct EngineStats {
   uint64_t host_cache_stores = 0;
   uint64_t writeback_flushes = 0;
   uint64_t errors = 0;
+  uint64_t checksum_failures = 0;  // records that failed verification
   double avg_write_seconds = 0;
   uint64_t bytes_stored = 0;
   uint64_t bytes_loaded = 0;
@@ -199,7 +218,13 @@ class StorageOffloadEngine {
       throw std::invalid_argument(
           "fp8_group_size must be 64, 128, 256 or 512 (got " +
           std::to_string(cfg_.fp8_group_size) + ")");
+    // Staging is sized from raw block_bytes (the fp8 layouts are smaller and
+    // the split fp8 gather keeps its scratch in the difference). With
+    // footers raw is block_bytes + 16 per tile and nothing is left over, so
+    // that mode sizes every buffer from the real record stride and gives
+    // the device bounce its scratch tail explicitly.
     size_t max_file_bytes = 0;
+    size_t max_device_bytes = 0;
     for (size_t gi = 0; gi < groups_.size(); ++gi) {
       auto& g = groups_[gi];
       if (g.block_bytes % 16 != 0)
@@ -212,9 +237,19 @@ class StorageOffloadEngine {
             std::to_string(cfg_.fp8_group_size));
       if (g.layer_ptrs.size() != g.layer_strides.size())
         throw std::invalid_argument("layer ptr/stride length mismatch");
-      max_file_bytes =
-          std::max(max_file_bytes, static_cast<size_t>(cfg_.gpu_blocks_per_file) *
-                                       g.layer_ptrs.size() * g.block_bytes);
+      if (cfg_.checksum) {
+        const size_t tiles =
+            static_cast<size_t>(cfg_.gpu_blocks_per_file) * g.layer_ptrs.size();
+        const size_t fb = tiles * tile_record_bytes(g);
+        max_file_bytes = std::max(max_file_bytes, fb);
+        max_device_bytes =
+            std::max(max_device_bytes, align16(fb) + scratch_bytes(tiles));
+      } else {
+        max_file_bytes = std::max(
+            max_file_bytes, static_cast<size_t>(cfg_.gpu_blocks_per_file) *
+                                g.layer_ptrs.size() * g.block_bytes);
+        max_device_bytes = max_file_bytes;
+      }
       if (cfg_.gpu_mode) {
         void* dp = nullptr;
         KVO_HIP_CHECK(hipMalloc(&dp, g.layer_ptrs.size() * sizeof(void*)));
@@ -231,11 +266,13 @@ class StorageOffloadEngine {
       }
     }
 
-    size_t device_staging = cfg_.copy_path == CopyPath::kStaged ? max_file_bytes : 0;
+    size_t device_staging =
+        cfg_.copy_path == CopyPath::kStaged ? max_device_bytes : 0;
     bool mapped = cfg_.copy_path == CopyPath::kZeroCopy;
     pool_ = std::make_unique<IoThreadPool>(
         cfg_.io_threads, cfg_.gpu_mode, cfg_.device, max_file_bytes, device_staging,
-        cfg_.read_preferring_ratio, mapped);
+        cfg_.read_preferring_ratio, mapped,
+        /*verify_result=*/cfg_.checksum && cfg_.copy_path == CopyPath::kStaged);
     if (cfg_.gpu_mode && cfg_.copy_path == CopyPath::kStaged)
       mover_ = std::make_unique<PcieMover>(true, cfg_.device);
     if (cfg_.host_cache_bytes > 0 && cfg_.copy_path != CopyPath::kZeroCopy &&
@@ -427,6 +464,7 @@ class StorageOffloadEngine {
       out.host_cache_stores += s.host_cache_stores;
       out.writeback_flushes += s.writeback_flushes;
       out.errors += s.errors;
+      out.checksum_failures += s.checksum_failures;
       out.bytes_stored += s.bytes_stored;
       out.bytes_loaded += s.bytes_loaded;
       out.t_gather_ms += s.t_gather_ms;
@@ -548,7 +586,8 @@ class StorageOffloadEngine {
     }
   }
 
-  size_t tile_record_bytes(const GroupDesc& g) const {
+  // Bytes of a tile record before the optional checksum footer.
+  size_t tile_payload_bytes(const GroupDesc& g) const {
     switch (cfg_.serialize) {
       case Serialize::kFp8E4M3:
         return g.block_bytes / 2 + 4;
@@ -557,6 +596,64 @@ class StorageOffloadEngine {
       default:
         return g.block_bytes;
     }
+  }
+
+  uint32_t footer_bytes() const {
+    return cfg_.checksum ? static_cast<uint32_t>(kChecksumFooterBytes) : 0;
+  }
+
+  size_t tile_record_bytes(const GroupDesc& g) const {
+    return tile_payload_bytes(g) + footer_bytes();
+  }
+
+  static size_t align16(size_t n) { return (n + 15) & ~static_cast<size_t>(15); }
+
+  // Device scratch behind a checksummed slab of `tiles` records: the
+  // partial sums of seal/verify, which also covers the partial maxima of
+  // the split fp8 gather (4 bytes each where these take 8, and consumed
+  // on the same stream before seal starts).
+  static size_t scratch_bytes(size_t tiles) {
+    return kvc_checksum_scratch_bytes(tiles);
+  }
+
+  uint64_t* checksum_scratch(WorkerCtx& ctx, size_t bytes) const {
+    return reinterpret_cast<uint64_t*>(ctx.device_staging->ptr() +
+                                       align16(bytes));
+  }
+
+  struct ChecksumError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+  };
+
+  // A span failed verification: count it, remove every copy that could
+  // fail again (the store path skips files that exist, so a poisoned file
+  // would otherwise fail forever), and fail the task. The caller has not
+  // written a KV page yet; an in-flight fill slot is abandoned by its guard.
+  [[noreturn]] void checksum_failed(const FileTransfer& ft, size_t nl,
+                                    size_t bad, int64_t first,
+                                    const char* source) {
+    stats_inc([&](EngineStats& s) { s.checksum_failures += bad; });
+    if (cache_) cache_->invalidate(ft.path);
+    ::unlink(ft.path.c_str());
+    const int64_t tile = static_cast<int64_t>(ft.slot_offset) *
+                             static_cast<int64_t>(nl) + first;
+    throw ChecksumError("checksum mismatch in " + std::string(source) + " " +
+                        ft.path + ": " + std::to_string(bad) +
+                        " bad record(s), first bad tile " +
+                        std::to_string(tile) + " (block slot " +
+                        std::to_string(tile / static_cast<int64_t>(nl)) +
+                        ", layer " +
+                        std::to_string(tile % static_cast<int64_t>(nl)) +
+                        "); copy removed");
+  }
+
+  void verify_host(const FileTransfer& ft, const GroupDesc& g, size_t tiles,
+                   const uint8_t* slab, const char* source) {
+    int64_t first = -1;
+    const size_t bad =
+        verify_records_host(slab, tiles, tile_payload_bytes(g), &first);
+    if (bad != 0)
+      checksum_failed(ft, g.layer_ptrs.size(), bad, first, source);
   }
 
   size_t file_bytes(const GroupDesc& g, size_t n_blocks) const {
@@ -616,6 +713,9 @@ class StorageOffloadEngine {
 
     if (cfg_.copy_path == CopyPath::kHostMemcpy) {
       gather_host(g, ft.block_ids, host_buf);
+      if (cfg_.checksum)
+        seal_records_host(host_buf, static_cast<size_t>(nb) * nl,
+                          tile_payload_bytes(g));
       if (cfg_.write_policy == WritePolicy::kBack && slot != nullptr) {
         guard.ok = true;
         cache_->addref(slot);
@@ -659,7 +759,7 @@ class StorageOffloadEngine {
             const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
             dev_layer_strides_[ft.group], nl, g.block_bytes,
             cfg_.fp8_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
-            ctx.stream);
+            ctx.stream, footer_bytes());
       } else if (cfg_.serialize == Serialize::kFp8E4M3) {
         if (cfg_.copy_path == CopyPath::kStaged) {
           // split amax+quantize (chip-filling); the partial-max scratch
@@ -673,22 +773,32 @@ class StorageOffloadEngine {
               const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
               dev_layer_strides_[ft.group], nl, g.block_bytes,
               ft.block_ids.data(), nb, ids_dev, kernel_dst, scratch,
-              ctx.stream);
+              ctx.stream, footer_bytes());
         } else {
           // zero-copy writes pinned host directly: atomics over PCIe are
           // pathological, keep the fused single-workgroup variant
           err = kvc_launch_gather_fp8(
               const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
               dev_layer_strides_[ft.group], nl, g.block_bytes,
-              ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream);
+              ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream,
+              footer_bytes());
         }
       } else {
         err = kvc_launch_gather(
             const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
             dev_layer_strides_[ft.group], nl, g.block_bytes,
-            ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream);
+            ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream,
+            footer_bytes());
       }
       if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+      if (cfg_.checksum && cfg_.copy_path == CopyPath::kStaged) {
+        // seal on the bounce, behind the gather and ahead of gather_done:
+        // every staged branch below ships footers with its first D2H
+        err = kvc_launch_seal_records(
+            kernel_dst, static_cast<uint32_t>(nb) * nl, tile_payload_bytes(g),
+            checksum_scratch(ctx, bytes), ctx.stream);
+        if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+      }
       double t1 = now_s();
       stats_inc([&](EngineStats& s) { s.t_gather_ms += (t1 - t0) * 1e3; });
       if (cfg_.copy_path == CopyPath::kStaged &&
@@ -846,6 +956,11 @@ class StorageOffloadEngine {
         return false;
       }
       KVO_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+      // zero-copy: the records already sit in pinned host memory; a device
+      // pass would read them back across PCIe, so the host twin seals them
+      if (cfg_.checksum)
+        seal_records_host(host_buf, static_cast<size_t>(nb) * nl,
+                          tile_payload_bytes(g));
       double t2 = now_s();
       stats_inc([&](EngineStats& s) { s.t_d2h_ms += (t2 - t1) * 1e3; });
     }
@@ -876,15 +991,16 @@ class StorageOffloadEngine {
       case Serialize::kFp8E4M3Group:
         return kvc_launch_scatter_fp8_group(
             ptrs, strides, nl, g.block_bytes, cfg_.fp8_group_size,
-            ft.block_ids.data(), nb, ids_dev, src, ctx.stream);
+            ft.block_ids.data(), nb, ids_dev, src, ctx.stream,
+            footer_bytes());
       case Serialize::kFp8E4M3:
         return kvc_launch_scatter_fp8(ptrs, strides, nl, g.block_bytes,
                                       ft.block_ids.data(), nb, ids_dev, src,
-                                      ctx.stream);
+                                      ctx.stream, footer_bytes());
       default:
         return kvc_launch_scatter(ptrs, strides, nl, g.block_bytes,
                                   ft.block_ids.data(), nb, ids_dev, src,
-                                  ctx.stream);
+                                  ctx.stream, footer_bytes());
     }
   }
 
@@ -963,6 +1079,23 @@ class StorageOffloadEngine {
       double h0 = now_s();
       for (auto& f : futs) f.get();
       t_h2d = now_s() - h0;
+      if (cfg_.checksum) {
+        // verify the whole span on the bounce and read the verdict BEFORE
+        // the scatter is launched: a bad record must not reach a KV page
+        const uint32_t tiles = static_cast<uint32_t>(nb) * nl;
+        ctx.verify_result[0] = 0xffffffffu;  // overwritten by the kernel
+        ctx.verify_result[1] = 0;
+        hipError_t verr = kvc_launch_verify_records(
+            ctx.device_staging->ptr(), tiles, tile_payload_bytes(g),
+            checksum_scratch(ctx, bytes), ctx.verify_result_dev, ctx.stream);
+        if (verr != hipSuccess) throw HipError(hipGetErrorString(verr));
+        KVO_HIP_CHECK(hipStreamSynchronize(ctx.stream));
+        const uint32_t bad = ctx.verify_result[0];
+        if (bad != 0)
+          checksum_failed(ft, nl, bad > tiles ? tiles : bad,
+                          bad > tiles ? 0 : ctx.verify_result[1],
+                          hit ? "DRAM-tier copy of" : "file");
+      }
       touch_atime(ft.path);
       const int32_t* ids_dev = stage_ids(ctx, ft);
       hipError_t err =
@@ -986,6 +1119,18 @@ class StorageOffloadEngine {
     if (cfg_.copy_path == CopyPath::kHostMemcpy && cache_) {
       HostPinnedCache::Slot* hit = cache_->lookup(ft.path);
       if (hit && hit->bytes_used >= offset + bytes) {
+        if (cfg_.checksum) {
+          struct Release {
+            HostPinnedCache* c;
+            HostPinnedCache::Slot* s;
+            ~Release() {
+              if (s) c->release(s);
+            }
+          } rel{cache_.get(), hit};
+          verify_host(ft, g, static_cast<size_t>(nb) * nl,
+                      hit->buf->host() + offset, "DRAM-tier copy of");
+          rel.s = nullptr;
+        }
         scatter_host(g, ft.block_ids, hit->buf->host() + offset);
         touch_atime(ft.path);
         cache_->release(hit);
@@ -1004,6 +1149,11 @@ class StorageOffloadEngine {
     touch_atime(ft.path);
     double t1 = now_s();
     stats_inc([&](EngineStats& s) { s.t_read_ms += (t1 - t0) * 1e3; });
+    // host and zero-copy: the span sits in host memory, the host twin checks
+    // it before scatter_host / the scatter launch
+    if (cfg_.checksum)
+      verify_host(ft, g, static_cast<size_t>(nb) * nl,
+                  ctx.host_staging->host(), "file");
 
     if (cfg_.copy_path == CopyPath::kHostMemcpy) {
       scatter_host(g, ft.block_ids, ctx.host_staging->host());
@@ -1144,10 +1294,11 @@ class StorageOffloadEngine {
 
   public:
   // Shared software fp8 path (BlockCopier's host mode reuses it).
+  // footer: bytes every record carries behind its payload (0 or 16).
   static void host_fp8_copy(const GroupDesc& g, const std::vector<int32_t>& ids,
-                            uint8_t* packed, bool quantize) {
+                            uint8_t* packed, bool quantize, size_t footer = 0) {
     const size_t nl = g.layer_ptrs.size();
-    const size_t rec = g.block_bytes / 2 + 4;
+    const size_t rec = g.block_bytes / 2 + 4 + footer;
     for (size_t bi = 0; bi < ids.size(); ++bi) {
       for (size_t l = 0; l < nl; ++l) {
         uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +
@@ -1171,9 +1322,10 @@ class StorageOffloadEngine {
   static void host_fp8_group_copy(const GroupDesc& g,
                                   const std::vector<int32_t>& ids,
                                   uint8_t* packed, int group_size,
-                                  bool quantize) {
+                                  bool quantize, size_t footer = 0) {
     const size_t nl = g.layer_ptrs.size();
-    const size_t rec = fp8_group_record_bytes(g.block_bytes, group_size);
+    const size_t rec =
+        fp8_group_record_bytes(g.block_bytes, group_size) + footer;
     for (size_t bi = 0; bi < ids.size(); ++bi) {
       for (size_t l = 0; l < nl; ++l) {
         uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +

@@ -103,6 +103,21 @@ class HostPinnedCache {
     lru_.splice(lru_.end(), lru_, s->lru_it);  // immediate eviction candidate
   }
 
+  // Drop a published entry whose bytes turned out to be bad (a checksum
+  // mismatch on a hit): later lookups miss and a later store or miss-fill
+  // may cache the key afresh. Holders of the slot keep their reference and
+  // release() it as usual; an entry still being filled is left alone.
+  void invalidate(const std::string& key) {
+    std::lock_guard<std::mutex> g(mu_);
+    auto it = map_.find(key);
+    if (it == map_.end() || !it->second->valid) return;
+    Slot* s = it->second;
+    map_.erase(it);
+    s->key.clear();
+    s->valid = false;
+    lru_.splice(lru_.end(), lru_, s->lru_it);  // first eviction candidate
+  }
+
   void release(Slot* s) {
     std::lock_guard<std::mutex> g(mu_);
     s->refs--;

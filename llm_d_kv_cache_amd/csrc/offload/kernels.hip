@@ -46,7 +46,10 @@ __device__ __forceinline__ int32_t block_id(const BlockList& bl,
 // ---- gather / scatter (large tiles: 2D grid) --------------------------------
 // Tile (bi, l): block_bytes contiguous bytes.
 //   device side: layer_ptrs[l] + ids[bi] * layer_strides[l]
-//   staging side: dst + (bi * num_layers + l) * block_bytes
+//   staging side: dst + (bi * num_layers + l) * (block_bytes + footer_bytes)
+// footer_bytes is 0 for today's dense layout and 16 when records carry a
+// checksum footer (see kvc_seal_records below); every gather/scatter kernel
+// takes it as its last argument and only the record stride depends on it.
 // Grid: x = tile index, y = slices per tile (grid-stride inside the tile).
 // 16-byte vectors; block_bytes % 16 == 0 (host-checked).
 
@@ -54,15 +57,16 @@ __global__ __launch_bounds__(256) void kvc_gather_blocks(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst) {
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
   const uint4* __restrict__ src = reinterpret_cast<const uint4*>(
       static_cast<const uint8_t*>(layer_ptrs[l]) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
-  uint4* __restrict__ out =
-      reinterpret_cast<uint4*>(dst + static_cast<uint64_t>(tile) * block_bytes);
+  uint4* __restrict__ out = reinterpret_cast<uint4*>(
+      dst + static_cast<uint64_t>(tile) * (block_bytes + footer_bytes));
   const uint64_t nvec = block_bytes / 16;
   const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
   for (uint64_t v = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
@@ -74,7 +78,8 @@ __global__ __launch_bounds__(256) void kvc_scatter_blocks(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src) {
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
@@ -82,7 +87,7 @@ __global__ __launch_bounds__(256) void kvc_scatter_blocks(
       static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
   const uint4* __restrict__ in = reinterpret_cast<const uint4*>(
-      src + static_cast<uint64_t>(tile) * block_bytes);
+      src + static_cast<uint64_t>(tile) * (block_bytes + footer_bytes));
   const uint64_t nvec = block_bytes / 16;
   const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
   for (uint64_t v = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
@@ -163,7 +168,8 @@ inline dim3 copy_grid(uint32_t tiles, uint64_t block_bytes) {
 extern "C" hipError_t kvc_launch_gather(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
-    int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream) {
+    int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream,
+    uint32_t footer_bytes) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -173,7 +179,7 @@ extern "C" hipError_t kvc_launch_gather(
   dim3 grid = copy_grid(tiles, block_bytes);
   hipLaunchKernelGGL(kvc_gather_blocks, grid, dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, dst);
+                     bl, ids_dev, dst, footer_bytes);
   return hipGetLastError();
 }
 
@@ -181,7 +187,7 @@ extern "C" hipError_t kvc_launch_scatter(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, const uint8_t* src,
-    hipStream_t stream) {
+    hipStream_t stream, uint32_t footer_bytes) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -191,7 +197,7 @@ extern "C" hipError_t kvc_launch_scatter(
   dim3 grid = copy_grid(tiles, block_bytes);
   hipLaunchKernelGGL(kvc_scatter_blocks, grid, dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, src);
+                     bl, ids_dev, src, footer_bytes);
   return hipGetLastError();
 }
 
@@ -292,12 +298,12 @@ __global__ __launch_bounds__(256) void kvc_fp8_quant(
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
     const int32_t* __restrict__ ids_dev, const float* __restrict__ scales,
-    uint8_t* __restrict__ dst) {
+    uint8_t* __restrict__ dst, uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
   const uint64_t n_elems = block_bytes / 2;
-  const uint64_t record = n_elems + 4;
+  const uint64_t record = n_elems + 4 + footer_bytes;
   const uint16_t* __restrict__ src = reinterpret_cast<const uint16_t*>(
       static_cast<const uint8_t*>(layer_ptrs[l]) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
@@ -344,12 +350,13 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst) {
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
   const uint64_t n_elems = block_bytes / 2;  // bf16 elements per tile
-  const uint64_t record = n_elems + 4;       // payload + f32 scale
+  const uint64_t record = n_elems + 4 + footer_bytes;  // payload + f32 scale
   const uint16_t* __restrict__ src = reinterpret_cast<const uint16_t*>(
       static_cast<const uint8_t*>(layer_ptrs[l]) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
@@ -417,12 +424,13 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src) {
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
   const uint64_t n_elems = block_bytes / 2;
-  const uint64_t record = n_elems + 4;
+  const uint64_t record = n_elems + 4 + footer_bytes;
   uint16_t* __restrict__ out = reinterpret_cast<uint16_t*>(
       static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
@@ -456,7 +464,8 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8(
 extern "C" hipError_t kvc_launch_gather_fp8(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
-    int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream) {
+    int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream,
+    uint32_t footer_bytes) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -465,7 +474,7 @@ extern "C" hipError_t kvc_launch_gather_fp8(
   int tiles = num_blocks * num_layers;
   hipLaunchKernelGGL(kvc_gather_fp8, dim3(tiles), dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, dst);
+                     bl, ids_dev, dst, footer_bytes);
   return hipGetLastError();
 }
 
@@ -475,7 +484,7 @@ extern "C" hipError_t kvc_launch_gather_fp8_split(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, uint8_t* dst,
-    float* scales_scratch, hipStream_t stream) {
+    float* scales_scratch, hipStream_t stream, uint32_t footer_bytes) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -488,7 +497,7 @@ extern "C" hipError_t kvc_launch_gather_fp8_split(
                      bl, ids_dev, scales_scratch);
   hipLaunchKernelGGL(kvc_fp8_quant, grid, dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, scales_scratch, dst);
+                     bl, ids_dev, scales_scratch, dst, footer_bytes);
   return hipGetLastError();
 }
 
@@ -496,7 +505,7 @@ extern "C" hipError_t kvc_launch_scatter_fp8(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, const uint8_t* src,
-    hipStream_t stream) {
+    hipStream_t stream, uint32_t footer_bytes) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -506,7 +515,7 @@ extern "C" hipError_t kvc_launch_scatter_fp8(
   dim3 grid = copy_grid(tiles, block_bytes);
   hipLaunchKernelGGL(kvc_scatter_fp8, grid, dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, src);
+                     bl, ids_dev, src, footer_bytes);
   return hipGetLastError();
 }
 
@@ -532,7 +541,8 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8_group(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst) {
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
   static_assert(kLanes == 8 || kLanes == 16 || kLanes == 32 || kLanes == 64,
                 "group must span 8..64 lanes of one wave");
   const uint32_t tile = blockIdx.x;
@@ -540,7 +550,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8_group(
   const int bi = tile / num_layers;
   const uint64_t n_elems = block_bytes / 2;
   const uint64_t n_groups = n_elems / (8 * kLanes);
-  const uint64_t record = n_elems + 4 * n_groups;
+  const uint64_t record = n_elems + 4 * n_groups + footer_bytes;
   const uint4* __restrict__ vsrc = reinterpret_cast<const uint4*>(
       static_cast<const uint8_t*>(layer_ptrs[l]) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
@@ -594,13 +604,14 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8_group(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
     uint64_t block_bytes, int lane_shift, BlockList blocks,
-    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src) {
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
   const uint64_t n_elems = block_bytes / 2;
   const uint64_t nvec = n_elems / 8;
-  const uint64_t record = n_elems + 4 * (nvec >> lane_shift);
+  const uint64_t record = n_elems + 4 * (nvec >> lane_shift) + footer_bytes;
   uint4* __restrict__ vout = reinterpret_cast<uint4*>(
       static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
       static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
@@ -654,7 +665,7 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, int group_size,
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
-    uint8_t* dst, hipStream_t stream) {
+    uint8_t* dst, hipStream_t stream, uint32_t footer_bytes) {
   const int shift = fp8_group_lane_shift(block_bytes, group_size);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
@@ -667,7 +678,7 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
 #define KVC_GATHER_GROUP(LANES)                                               \
   hipLaunchKernelGGL(kvc_gather_fp8_group<LANES>, grid, dim3(256), 0, stream, \
                      layer_ptrs_dev, layer_strides_dev, num_layers,           \
-                     block_bytes, bl, ids_dev, dst)
+                     block_bytes, bl, ids_dev, dst, footer_bytes)
   switch (shift) {
     case 3: KVC_GATHER_GROUP(8); break;
     case 4: KVC_GATHER_GROUP(16); break;
@@ -682,7 +693,7 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, int group_size,
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
-    const uint8_t* src, hipStream_t stream) {
+    const uint8_t* src, hipStream_t stream, uint32_t footer_bytes) {
   const int shift = fp8_group_lane_shift(block_bytes, group_size);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
@@ -694,7 +705,195 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
   dim3 grid = copy_grid(tiles, block_bytes);
   hipLaunchKernelGGL(kvc_scatter_fp8_group, grid, dim3(256), 0, stream,
                      layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     shift, bl, ids_dev, src);
+                     shift, bl, ids_dev, src, footer_bytes);
+  return hipGetLastError();
+}
+
+
+// ---- per-record checksums ----------------------------------------------------
+// EngineConfig::checksum appends a 16-byte footer to every tile record:
+//   [ payload (P bytes, P % 4 == 0) | sum u64 | magic "KVCS" | P as u32 ]
+// sum = SUM_i mix(((i + 1) << 32) | w[i]) mod 2^64 over the payload's u32
+// words, mix = the splitmix64 finalizer (checksum.h is the host twin and
+// must produce the same bytes). Addition commutes, so partial sums combine
+// in any order:
+//   pass 1 (kvc_record_partial_sums): grid (tile, slices) as the copy
+//     kernels; lane -> wave shuffle -> LDS -> one plain 64-bit store per
+//     workgroup to partials[tile * slices + slice] (no atomics, no memset —
+//     see kvc_fp8_amax for what a zero-init blit costs);
+//   pass 2 (kvc_seal_records / kvc_verify_records): adds the <= slices
+//     partials of a tile and writes, or compares, the footer.
+// fp8 records are only 4-byte aligned (stride n + 20), so pass 1 peels up to
+// three leading words to reach a 16-byte boundary, reads the body as
+// dwordx4 and picks up the <= 3 trailing words; the footer is written and
+// read as four dwords, never as one 8-byte access.
+
+namespace {
+
+constexpr uint32_t kCsumMagic = 0x5343564Bu;
+constexpr uint32_t kCsumFooterBytes = 16;
+
+__device__ __forceinline__ uint64_t csum_mix(uint64_t index, uint32_t word) {
+  uint64_t x = ((index + 1) << 32) | word;
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void kvc_record_partial_sums(
+    const uint8_t* __restrict__ slab, uint32_t payload_bytes,
+    uint64_t* __restrict__ partials) {
+  const uint32_t tile = blockIdx.x;
+  const uint8_t* __restrict__ rec =
+      slab + static_cast<uint64_t>(tile) * (payload_bytes + kCsumFooterBytes);
+  const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(rec);
+  const uint32_t nwords = payload_bytes / 4;
+  uint32_t head =
+      static_cast<uint32_t>((16 - (reinterpret_cast<uintptr_t>(rec) & 15)) & 15) / 4;
+  if (head > nwords) head = nwords;
+  const uint32_t nvec = (nwords - head) / 4;
+  const uint32_t tail = nwords - head - nvec * 4;
+  const uint4* __restrict__ body = reinterpret_cast<const uint4*>(words + head);
+  uint64_t acc = 0;
+  const uint32_t stride = gridDim.y * blockDim.x;
+  for (uint32_t v = blockIdx.y * blockDim.x + threadIdx.x; v < nvec;
+       v += stride) {
+    const uint4 w = body[v];
+    const uint64_t i = head + 4ull * v;
+    acc += csum_mix(i, w.x) + csum_mix(i + 1, w.y) + csum_mix(i + 2, w.z) +
+           csum_mix(i + 3, w.w);
+  }
+  // the <= 3 head and <= 3 tail words ride the first lanes of slice 0
+  if (blockIdx.y == 0 && threadIdx.x < head + tail) {
+    const uint32_t i = threadIdx.x < head
+                           ? threadIdx.x
+                           : head + nvec * 4 + (threadIdx.x - head);
+    acc += csum_mix(i, words[i]);
+  }
+  __shared__ uint64_t lds_sum[4];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) lds_sum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[static_cast<uint64_t>(tile) * gridDim.y + blockIdx.y] =
+        lds_sum[0] + lds_sum[1] + lds_sum[2] + lds_sum[3];
+}
+
+// One lane per record: writes the whole footer, whatever it held before.
+__global__ __launch_bounds__(256) void kvc_seal_records(
+    uint8_t* __restrict__ slab, uint32_t tiles, uint32_t payload_bytes,
+    const uint64_t* __restrict__ partials, uint32_t slices) {
+  const uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tile >= tiles) return;
+  uint64_t sum = 0;
+  for (uint32_t g = 0; g < slices; ++g)
+    sum += partials[static_cast<uint64_t>(tile) * slices + g];
+  uint32_t* __restrict__ footer = reinterpret_cast<uint32_t*>(
+      slab + static_cast<uint64_t>(tile) * (payload_bytes + kCsumFooterBytes) +
+      payload_bytes);
+  footer[0] = static_cast<uint32_t>(sum);
+  footer[1] = static_cast<uint32_t>(sum >> 32);
+  footer[2] = kCsumMagic;
+  footer[3] = payload_bytes;
+}
+
+// One workgroup walks every record and leaves result[0] = number of records
+// whose footer does not match, result[1] = index of the first one
+// (0xffffffff when none). Read-only on the slab; result needs no zero-init.
+__global__ __launch_bounds__(256) void kvc_verify_records(
+    const uint8_t* __restrict__ slab, uint32_t tiles, uint32_t payload_bytes,
+    const uint64_t* __restrict__ partials, uint32_t slices,
+    uint32_t* __restrict__ result) {
+  uint32_t bad = 0, first = 0xffffffffu;
+  for (uint32_t tile = threadIdx.x; tile < tiles; tile += blockDim.x) {
+    uint64_t sum = 0;
+    for (uint32_t g = 0; g < slices; ++g)
+      sum += partials[static_cast<uint64_t>(tile) * slices + g];
+    const uint32_t* __restrict__ footer = reinterpret_cast<const uint32_t*>(
+        slab + static_cast<uint64_t>(tile) * (payload_bytes + kCsumFooterBytes) +
+        payload_bytes);
+    const bool ok = footer[0] == static_cast<uint32_t>(sum) &&
+                    footer[1] == static_cast<uint32_t>(sum >> 32) &&
+                    footer[2] == kCsumMagic && footer[3] == payload_bytes;
+    if (!ok) {
+      ++bad;
+      first = first < tile ? first : tile;
+    }
+  }
+  __shared__ uint32_t lds_bad[4], lds_first[4];
+  for (int off = 32; off > 0; off >>= 1) {
+    bad += __shfl_down(bad, off, 64);
+    const uint32_t other = __shfl_down(first, off, 64);
+    first = first < other ? first : other;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    lds_bad[threadIdx.x >> 6] = bad;
+    lds_first[threadIdx.x >> 6] = first;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t f = lds_first[0];
+    for (int w = 1; w < 4; ++w) f = f < lds_first[w] ? f : lds_first[w];
+    result[0] = lds_bad[0] + lds_bad[1] + lds_bad[2] + lds_bad[3];
+    result[1] = f;
+  }
+}
+
+// Scratch the two checksum launchers need: one u64 per (tile, slice), and
+// copy_grid never makes more than tiles + 2048 workgroups.
+extern "C" size_t kvc_checksum_scratch_bytes(size_t tiles) {
+  return (tiles + 2048) * sizeof(uint64_t);
+}
+
+namespace {
+
+inline bool csum_args_ok(const void* slab, uint32_t tiles,
+                         uint64_t payload_bytes, const void* scratch) {
+  return tiles > 0 && payload_bytes > 0 && payload_bytes % 4 == 0 &&
+         payload_bytes <= 0xfffffff0ull &&
+         (reinterpret_cast<uintptr_t>(slab) & 3) == 0 &&
+         (reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && scratch != nullptr;
+}
+
+}  // namespace
+
+// slab: `tiles` records of payload_bytes + 16, 4-byte aligned; scratch:
+// kvc_checksum_scratch_bytes(tiles) of 8-byte aligned device memory.
+extern "C" hipError_t kvc_launch_seal_records(uint8_t* slab, uint32_t tiles,
+                                              uint64_t payload_bytes,
+                                              uint64_t* scratch,
+                                              hipStream_t stream) {
+  if (!csum_args_ok(slab, tiles, payload_bytes, scratch))
+    return hipErrorInvalidValue;
+  const uint32_t pb = static_cast<uint32_t>(payload_bytes);
+  dim3 grid = copy_grid(tiles, payload_bytes);
+  hipLaunchKernelGGL(kvc_record_partial_sums, grid, dim3(256), 0, stream, slab,
+                     pb, scratch);
+  hipLaunchKernelGGL(kvc_seal_records, dim3((tiles + 255) / 256), dim3(256), 0,
+                     stream, slab, tiles, pb, scratch, grid.y);
+  return hipGetLastError();
+}
+
+// result: two u32 the device can write (bad count, first bad index).
+extern "C" hipError_t kvc_launch_verify_records(const uint8_t* slab,
+                                                uint32_t tiles,
+                                                uint64_t payload_bytes,
+                                                uint64_t* scratch,
+                                                uint32_t* result,
+                                                hipStream_t stream) {
+  if (!csum_args_ok(slab, tiles, payload_bytes, scratch) || result == nullptr)
+    return hipErrorInvalidValue;
+  const uint32_t pb = static_cast<uint32_t>(payload_bytes);
+  dim3 grid = copy_grid(tiles, payload_bytes);
+  hipLaunchKernelGGL(kvc_record_partial_sums, grid, dim3(256), 0, stream, slab,
+                     pb, scratch);
+  hipLaunchKernelGGL(kvc_verify_records, dim3(1), dim3(256), 0, stream, slab,
+                     tiles, pb, scratch, grid.y, result);
   return hipGetLastError();
 }
 

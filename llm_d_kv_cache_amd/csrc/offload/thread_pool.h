@@ -31,6 +31,11 @@ struct WorkerCtx {
   HostStaging* host_staging = nullptr;    // pinned (GPU mode) or aligned malloc
   DeviceStaging* device_staging = nullptr;  // HBM bounce; empty in host mode
   int32_t* dev_ids = nullptr;  // device block-id buffer (> kernarg-limit paths)
+  // Verdict of kvc_verify_records (bad count, first bad index): two words of
+  // mapped pinned memory the kernel writes and the worker reads after its
+  // stream sync. Null unless the engine verifies checksums on the bounce.
+  volatile uint32_t* verify_result = nullptr;
+  uint32_t* verify_result_dev = nullptr;
 };
 
 // kHigh = loads, kNormal = store front halves (gather + D2H), kCont =
@@ -48,11 +53,12 @@ class IoThreadPool {
 
   IoThreadPool(int n_threads, bool gpu_mode, int device, size_t host_staging_bytes,
                size_t device_staging_bytes, double read_preferring_ratio,
-               bool mapped_host_staging = false)
+               bool mapped_host_staging = false, bool verify_result = false)
       : gpu_mode_(gpu_mode), device_(device),
         host_staging_bytes_(host_staging_bytes),
         device_staging_bytes_(device_staging_bytes),
-        mapped_host_staging_(mapped_host_staging) {
+        mapped_host_staging_(mapped_host_staging),
+        verify_result_(verify_result) {
     n_threads = std::max(1, n_threads);
     int numa_node = -1;
     if (gpu_mode_) {
@@ -126,6 +132,7 @@ class IoThreadPool {
     ctx.worker_id = i;
     std::unique_ptr<HostStaging> host_staging;
     std::unique_ptr<DeviceStaging> device_staging;
+    std::unique_ptr<HostStaging> verify_result;
     try {
       if (gpu_mode_) {
         KVO_HIP_CHECK(hipSetDevice(device_));
@@ -140,6 +147,12 @@ class IoThreadPool {
           std::make_unique<DeviceStaging>(device_staging_bytes_, gpu_mode_);
       ctx.host_staging = host_staging.get();
       ctx.device_staging = device_staging.get();
+      if (gpu_mode_ && verify_result_) {
+        verify_result = std::make_unique<HostStaging>(64, true, /*mapped=*/true);
+        ctx.verify_result = reinterpret_cast<uint32_t*>(verify_result->host());
+        ctx.verify_result_dev =
+            reinterpret_cast<uint32_t*>(verify_result->device());
+      }
     } catch (const std::exception& e) {
       std::lock_guard<std::mutex> g(mu_);
       init_error_ = e.what();
@@ -194,6 +207,7 @@ class IoThreadPool {
   size_t host_staging_bytes_;
   size_t device_staging_bytes_;
   bool mapped_host_staging_ = false;
+  bool verify_result_ = false;
   std::vector<int> cpus_;
   std::mutex mu_;
   std::condition_variable cv_;

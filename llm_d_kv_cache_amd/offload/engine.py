@@ -30,27 +30,38 @@ class OffloadEngineConfig:
     host_cache_bytes: int = 0  # pinned-DRAM cache tier (0 = off)
     write_policy: str = "through"  # through | back (flush async via DRAM tier)
     direct_io: bool = False    # O_DIRECT for NVMe (auto-fallback elsewhere)
+    # per-record checksums: every (block, layer) record gains a 16-byte
+    # footer, sealed on store and verified on load before any KV page is
+    # written. Give the FileMapper a dtype tag ending in "+ck" so files with
+    # and without footers never share a directory.
+    checksum: bool = False
     device: int = 0
     staging_budget_bytes: int = DEFAULT_STAGING_BUDGET_BYTES
 
 
 SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group")
 FP8_GROUP_SIZES = (64, 128, 256, 512)
+CHECKSUM_FOOTER_BYTES = 16
+CHECKSUM_MAGIC = 0x5343564B  # the bytes "KVCS"
+# suffix of the FileMapper dtype tag that keeps checksummed files apart
+CHECKSUM_DTYPE_SUFFIX = "+ck"
 
 
 def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
-                      group: int = 0) -> int:
+                      group: int = 0, checksum: bool = False) -> int:
     """Bytes one (block, layer) tile occupies in a file/object/slab.
 
     raw: block_bytes. fp8_e4m3: n + 4 (n = block_bytes/2 fp8 bytes, one f32
     scale). fp8_e4m3_group: n + 4*n/G (one f32 scale per G elements).
+    checksum=True adds the 16-byte footer (sum u64, magic, payload bytes).
     Raises ValueError for an unknown mode, a group size outside
     FP8_GROUP_SIZES, or a KV group whose tile G does not divide.
     """
+    footer = CHECKSUM_FOOTER_BYTES if checksum else 0
     if serialize == "raw":
-        return block_bytes
+        return block_bytes + footer
     if serialize == "fp8_e4m3":
-        return block_bytes // 2 + 4
+        return block_bytes // 2 + 4 + footer
     if serialize != "fp8_e4m3_group":
         raise ValueError(
             f"serialize must be one of {'|'.join(SERIALIZE_MODES)}, "
@@ -64,7 +75,17 @@ def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
         raise ValueError(
             f"KV group {group}: block_bytes={block_bytes} holds {n} bf16 "
             f"elements, not a multiple of fp8_group_size={fp8_group_size}")
-    return n + 4 * (n // fp8_group_size)
+    return n + 4 * (n // fp8_group_size) + footer
+
+
+def record_checksum(buffer) -> int:
+    """The ``sum`` field of a record's checksum footer, computed on the host
+    over ``buffer`` (bytes-like or a C-contiguous array; length a multiple
+    of 4): sum of splitmix64-finalized ``((i + 1) << 32) | word[i]`` mod
+    2**64. Same value the seal/verify kernels compute."""
+    from .. import ensure_offload_native
+
+    return int(ensure_offload_native().record_checksum(buffer))
 
 
 class TorchOffloadEngine:
@@ -103,6 +124,7 @@ class TorchOffloadEngine:
         native_groups = []
         self.group_geometry: List[dict] = []
         max_file_bytes = 0
+        max_device_bytes = 0
         for gi, g in enumerate(groups):
             ptrs = [t.data_ptr() for t in g]
             strides = [t.stride(0) * t.element_size() for t in g]
@@ -113,12 +135,14 @@ class TorchOffloadEngine:
             # the actual payload per block may be smaller than the stride;
             # canonical layouts are dense so stride == payload
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
+            footer = CHECKSUM_FOOTER_BYTES if config.checksum else 0
             if config.serialize == "fp8_e4m3_group":
                 record_bytes = tile_record_bytes(
-                    config.serialize, bb, config.fp8_group_size, gi)
+                    config.serialize, bb, config.fp8_group_size, gi,
+                    config.checksum)
             else:
-                record_bytes = (bb // 2 + 4 if config.serialize == "fp8_e4m3"
-                                else bb)
+                record_bytes = footer + (
+                    bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb)
             self.group_geometry.append(
                 {
                     "num_layers": len(g),
@@ -127,13 +151,24 @@ class TorchOffloadEngine:
                     "num_device_blocks": g[0].shape[0],
                 }
             )
-            max_file_bytes = max(
-                max_file_bytes, config.gpu_blocks_per_file * len(g) * bb
-            )
+            # mirrors the native engine's staging sizes: raw block_bytes per
+            # tile, or with footers the real record stride and, behind the
+            # device bounce, the seal/verify scratch (8 bytes per workgroup,
+            # at most tiles + 2048 of them)
+            tiles = config.gpu_blocks_per_file * len(g)
+            if config.checksum:
+                fb = tiles * record_bytes
+                max_file_bytes = max(max_file_bytes, fb)
+                max_device_bytes = max(
+                    max_device_bytes, (fb + 15) // 16 * 16 + (tiles + 2048) * 8)
+            else:
+                max_file_bytes = max(max_file_bytes, tiles * bb)
+                max_device_bytes = max_file_bytes
 
         # staging budget clamp: per worker we allocate host staging (and in
-        # staged mode an equal device bounce)
-        per_thread = max_file_bytes * (2 if config.copy_path == "staged" else 1)
+        # staged mode a device bounce)
+        per_thread = max_file_bytes + (
+            max_device_bytes if config.copy_path == "staged" else 0)
         io_threads = config.io_threads
         if per_thread > 0:
             budget_threads = max(1, config.staging_budget_bytes // per_thread)
@@ -157,6 +192,7 @@ class TorchOffloadEngine:
             write_policy=config.write_policy,
             direct_io=config.direct_io,
             fp8_group_size=config.fp8_group_size,
+            checksum=config.checksum,
         )
         del stream
         # keep tensor refs: the native engine holds raw pointers
@@ -219,7 +255,10 @@ class TorchOffloadEngine:
         first n_blocks' packed bytes, or None on a cache miss / short
         entry. The payload layout matches the file layout (raw gather
         layout, per-tile fp8 records when serialize="fp8_e4m3", group-scaled
-        fp8 records when serialize="fp8_e4m3_group")."""
+        fp8 records when serialize="fp8_e4m3_group"). With checksum=True
+        every record in the returned slab still carries its 16-byte footer
+        (record stride = group_geometry[group]["record_bytes"]); the slab is
+        handed out as stored, it is not verified here."""
         import torch
 
         geo = self.group_geometry[group]

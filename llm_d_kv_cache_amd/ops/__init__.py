@@ -14,6 +14,11 @@ built from, for embedding in other MI355X services.
   (64/128/256/512; set it to head_dim) instead of one per tile. The gather
   is a single pass — the group amax is an in-wave butterfly — and needs no
   scratch. serialize="fp8_e4m3_group" rides these kernels.
+- record checksums: packed_bytes*/gather*/scatter* take checksum=True to
+  leave a 16-byte footer behind every record; seal_records(ptr, tiles,
+  payload_bytes, stream) fills the footers of such a slab and
+  verify_records(...) returns (bad records, first bad index or -1).
+  record_checksum(buffer) is the host twin of the sum, for tools and tests.
 """
 from __future__ import annotations
 
@@ -36,6 +41,14 @@ def block_copier(groups: Sequence[Sequence], device: Optional[int] = None):
     dev = device if device is not None else (
         groups[0][0].device.index or 0 if gpu else 0)
     return ko.BlockCopier(native, gpu, dev)
+
+
+def record_checksum(buffer) -> int:
+    """Host twin of the seal/verify kernels' per-record sum (see
+    offload.engine.record_checksum)."""
+    from ..offload.engine import record_checksum as _rc
+
+    return _rc(buffer)
 
 
 def prefix_hash(tokens, seq_offsets, seeds, block_size: int = 16,

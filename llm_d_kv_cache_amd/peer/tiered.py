@@ -29,17 +29,22 @@ def make_dram_lookup(engine, mapper):
     The peer wire carries raw slabs or per-tile fp8 records only. An engine
     with serialize="fp8_e4m3_group" keeps group-scaled records in its DRAM
     tier, which the wire cannot label, so its lookup reports a miss every
-    time (logged once) and pulls fall through to the storage tier."""
-    if engine.config.serialize == "fp8_e4m3_group":
+    time (logged once) and pulls fall through to the storage tier. The same
+    holds for an engine with checksum=True: its DRAM-tier records carry
+    16-byte footers the wire does not understand."""
+    grouped = engine.config.serialize == "fp8_e4m3_group"
+    if grouped or getattr(engine.config, "checksum", False):
         warned = []
+        why = ("serialize='fp8_e4m3_group': the peer wire has no "
+               "group-scaled fp8 format" if grouped else
+               "checksum=True: the peer wire does not carry record footers")
 
         def never(chunk_hash, group, n_blocks):
             if not warned:
                 warned.append(True)
                 log.warning(
-                    "DRAM-tier peer serving is off for serialize="
-                    "'fp8_e4m3_group': the peer wire has no group-scaled "
-                    "fp8 format; pulls fall through to storage")
+                    "DRAM-tier peer serving is off for %s; pulls fall "
+                    "through to storage", why)
             return None
 
         return never
