@@ -1226,58 +1226,34 @@ class StorageOffloadEngine {
     uint32_t rounding = 0x7fff + ((w >> 16) & 1);
     return static_cast<uint16_t>((w + rounding) >> 16);
   }
-  static uint8_t f32_to_fp8(float x) {
-    // OCP e4m3fn: 1s 4e 3m, bias 7, max 448, no inf, single NaN.
-    if (x != x) return 0x7f;
-    uint8_t sign = x < 0 ? 0x80 : 0;
-    float a = std::abs(x);
-    if (a >= 448.0f) return sign | 0x7e;  // saturate to max normal
-    if (a < 0.0009765625f) {              // subnormal range (< 2^-10 = min subnormal/2... )
-      // subnormals: value = m * 2^-9, m in [0,7]
-      int m = static_cast<int>(a * 512.0f + 0.5f);
-      if (m > 7) m = 7;
-      return sign | static_cast<uint8_t>(m);
-    }
-    int e;
-    float frac = std::frexp(a, &e);  // a = frac * 2^e, frac in [0.5, 1)
-    // normalized: a = 1.mmm * 2^(e-1); exponent field = (e-1)+7
-    int exp_field = e - 1 + 7;
-    float mant = frac * 2.0f - 1.0f;  // [0,1)
-    int m = static_cast<int>(mant * 8.0f + 0.5f);
-    if (m == 8) {
-      m = 0;
-      exp_field += 1;
-    }
-    if (exp_field >= 16) return sign | 0x7e;
-    if (exp_field <= 0) {
-      // underflow into subnormal
-      int ms = static_cast<int>(a * 512.0f + 0.5f);
-      if (ms > 7) ms = 7;
-      return sign | static_cast<uint8_t>(ms);
-    }
-    return sign | static_cast<uint8_t>((exp_field << 3) | m);
-  }
-  // Round-to-nearest-even e4m3fn encoder of the group-scaled mode (the
-  // CDNA4 cvt_pk_fp8_f32 rounding; f32_to_fp8 above rounds ties upward
-  // and stays as the per-tile mode's codec). Finite inputs only; the sign
-  // survives a magnitude that rounds to zero.
+  // Round-to-nearest-even OCP e4m3fn encoder (1s 4e 3m, bias 7, max 448,
+  // no inf) of both fp8 modes: the CDNA4 cvt_pk_fp8_f32 rounding, ties to
+  // even, saturating at +-448. Finite inputs only (fp8_quantize_tile guards
+  // NaN itself); the sign survives a magnitude that rounds to zero.
+  // Branch-free, so the quantize loops vectorize and a tile of tiny scaled
+  // values (amax = Inf makes every one of them 0) costs no more than any
+  // other.
   static uint8_t f32_to_fp8_rne(float x) {
     uint32_t w;
     std::memcpy(&w, &x, 4);
-    const uint8_t sign = static_cast<uint8_t>((w >> 24) & 0x80);
+    const uint32_t sign = (w >> 24) & 0x80u;
     w &= 0x7fffffffu;
     float a;
     std::memcpy(&a, &w, 4);
-    if (a < 0.015625f) {
-      // below the min normal 2^-6: code = RNE(a / 2^-9) in [0, 8]; 8 is
-      // the encoding of 2^-6 itself. a * 512 is exact.
-      return sign | static_cast<uint8_t>(std::nearbyint(a * 512.0f));
-    }
+    // below the min normal 2^-6: code = RNE(a / 2^-9) in [0, 8]; 8 is the
+    // encoding of 2^-6 itself. a * 512 is exact, and adding 1.5 * 2^23
+    // leaves that integer, rounded to nearest even, in the low mantissa bits
+    const float f = a * 512.0f + 12582912.0f;
+    uint32_t sub;
+    std::memcpy(&sub, &f, 4);
+    sub &= 0xffu;
     // f32 bits >> 20 = (exponent << 3) | top-3 mantissa bits; rounding the
     // dropped 20 bits to even carries into the exponent by itself
-    w += 0x7ffffu + ((w >> 20) & 1);
-    const uint32_t code = (w >> 20) - ((127u - 7u) << 3);
-    return sign | static_cast<uint8_t>(code > 0x7e ? 0x7e : code);
+    const uint32_t r = w + 0x7ffffu + ((w >> 20) & 1);
+    uint32_t code = (r >> 20) - ((127u - 7u) << 3);
+    code = code > 0x7eu ? 0x7eu : code;
+    code = a < 0.015625f ? sub : code;
+    return static_cast<uint8_t>(sign | code);
   }
   static float fp8_to_f32(uint8_t b) {
     uint8_t sign = b & 0x80;
@@ -1384,8 +1360,12 @@ class StorageOffloadEngine {
     if (amax <= 0.0f) amax = 1.0f;
     float scale = amax / 448.0f;
     float inv = 448.0f / amax;
-    for (size_t i = 0; i < n; ++i)
-      out[i] = f32_to_fp8(bf16_to_f32(in[i]) * inv);
+    for (size_t i = 0; i < n; ++i) {
+      const float x = bf16_to_f32(in[i]) * inv;
+      // a NaN never enters amax (std::max keeps the other operand) and is
+      // stored as the e4m3fn NaN code, so it loads as NaN
+      out[i] = x != x ? 0x7f : f32_to_fp8_rne(x);
+    }
     std::memcpy(out + n, &scale, 4);
   }
 

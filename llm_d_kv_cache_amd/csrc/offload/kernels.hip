@@ -205,6 +205,7 @@ extern "C" hipError_t kvc_launch_prefix_hash(
     const uint32_t* tokens, const uint64_t* seq_off, const uint64_t* seeds,
     uint64_t* keys, const uint64_t* key_off, int block_size, int n_seq,
     hipStream_t stream) {
+  if (n_seq <= 0) return hipSuccess;  // nothing to hash; a 0-wide grid is an error
   int threads = 256;
   int blocks = (n_seq + threads - 1) / threads;
   hipLaunchKernelGGL(kvc_prefix_hash, dim3(blocks), dim3(threads), 0, stream,

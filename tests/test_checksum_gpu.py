@@ -67,12 +67,10 @@ def cpu_pages(shape):
     """CPU pages of one shape and the ids the tests move (the odd blocks);
     computed once, shared read-only.
 
-    The per-tile fp8 shape uses values that quantize exactly. On general
-    input the software per-tile encoder of host mode and v_cvt_pk_fp8_f32
-    do not round alike (with or without checksums: 12 of 3072 payload bytes
-    of randn pages of this shape differ, and engine.h keeps that encoder
-    "as the per-tile mode's codec"), which would make the byte comparison
-    with host mode a test of that encoder instead of the footers."""
+    The per-tile fp8 shape uses values that quantize exactly, so the byte
+    comparison with host mode here rests on the footers alone. (Host mode
+    and v_cvt_pk_fp8_f32 also agree on general input, ties included:
+    test_fp8_tile_gpu.py holds both to one oracle.)"""
     if shape not in _inputs:
         mode, bb, nl, nb = shape
         gen = torch.Generator().manual_seed(bb + nl + nb)
@@ -176,9 +174,8 @@ def test_gpu_file_equals_host_mode_file(tmp_path, shape, copy_path):
     """Byte for byte the file a host-mode engine writes for the same CPU
     pages.
 
-    The per-tile fp8 shape runs on exactly quantizable pages: see
-    cpu_pages for what differs on general input, and why that is not the
-    footers' doing.
+    The per-tile fp8 shape runs on exactly quantizable pages (see
+    cpu_pages); general input is compared in test_fp8_tile_gpu.py.
     """
     mode, bb, nl, nb = shape
     pages, ids = cpu_pages(shape)

@@ -11,6 +11,9 @@ go wrong:
                 a single 16-lane group
   64 KiB tiles  every group width (8/16/32/64 lanes), many slices
   160 blocks    ids through the device id buffer instead of the kernarg
+  8448 B x 8 x 128   1024 tiles: 2 slices of 256 lanes for 528 vectors, so
+                lanes take a second grid-stride trip, on which wave 0 of
+                slice 0 re-enters the shuffle with 48 dead lanes
 """
 import os
 
@@ -45,6 +48,7 @@ SHAPES = [
     (65536, 256, 4, 16),
     (65536, 512, 4, 16),
     (768, 128, 2, 160),
+    (8448, 128, 8, 128),
 ]
 SHAPE_IDS = [f"bb{b}-g{g}-l{l}-n{n}" for b, g, l, n in SHAPES]
 
@@ -122,7 +126,8 @@ def test_gpu_engine_roundtrip_matches_oracle(tmp_path, shape, copy_path):
     _check_loaded(dev_pages, shape)
 
 
-@pytest.mark.parametrize("shape", SHAPES[:6], ids=SHAPE_IDS[:6])
+@pytest.mark.parametrize("shape", SHAPES[:6] + SHAPES[7:],
+                         ids=SHAPE_IDS[:6] + SHAPE_IDS[7:])
 def test_gpu_block_copier_matches_oracle(shape):
     """BlockCopier.gather_fp8_group / scatter_fp8_group on device."""
     from llm_d_kv_cache_amd.ops import block_copier

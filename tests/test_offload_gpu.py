@@ -165,6 +165,137 @@ def test_prefix_hash_kernel_matches_cpu():
         assert list(got[s * n_chunks:(s + 1) * n_chunks]) == want
 
 
+# chain seeds at every CBOR width boundary of the parent field
+PREFIX_SEEDS = [0, 23, 24, 255, 256, 65535, 65536, 2**32 - 1, 2**32, 2**63,
+                2**64 - 1]
+# token classes by CBOR width: 1, 2, 3 and 5 bytes (the last split at 2^31,
+# where an int32 view turns negative)
+TOKEN_CLASSES = [(0, 23), (24, 255), (256, 65535), (65536, 2**31 - 1),
+                 (2**31, 2**32 - 1)]
+
+
+def _prefix_case(lengths, seed_shift, rng):
+    """Ragged sequences whose token at position i is of width class
+    (i + s) % 5 — so any sequence of five or more tokens holds every class,
+    its boundaries included — and seeds cycling through PREFIX_SEEDS."""
+    import numpy as np
+
+    lo_hi = np.array(TOKEN_CLASSES, dtype=np.int64)
+    seqs = []
+    for s, n in enumerate(lengths):
+        lo, hi = lo_hi[(np.arange(n) + s) % 5].T
+        pick = rng.integers(0, 4, n)
+        toks = np.where(pick == 0, lo, np.where(
+            pick == 1, hi, rng.integers(lo, hi + 1)))
+        seqs.append(toks.astype(np.uint32))
+    seeds = [PREFIX_SEEDS[(s + seed_shift) % len(PREFIX_SEEDS)]
+             for s in range(len(lengths))]
+    return seqs, seeds
+
+
+def _prefix_hash_on_gpu(seqs, seeds, block_size):
+    import numpy as np
+
+    from llm_d_kv_cache_amd.ops import prefix_hash
+
+    flat = np.concatenate(seqs) if seqs else np.empty(0, dtype=np.uint32)
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        off[1:] = np.cumsum([len(q) for q in seqs])
+    tokens = torch.from_numpy(flat.astype(np.uint32).view(np.int32)).cuda()
+    seeds_i64 = np.array(seeds, dtype=np.uint64).view(np.int64)
+    return prefix_hash(tokens, torch.from_numpy(off).cuda(),
+                       torch.from_numpy(seeds_i64).cuda(), block_size)
+
+
+def _prefix_oracle(seqs, seeds, block_size):
+    """The pure-Python chain of reference_impl, from the given seed."""
+    import reference_impl as ref
+
+    out = []
+    for toks, parent in zip(seqs, seeds):
+        keys = []
+        for c in range(len(toks) // block_size):
+            chunk = [int(t) for t in
+                     toks[c * block_size:(c + 1) * block_size]]
+            parent = ref.hash_block(parent, chunk, None)
+            keys.append(parent)
+        out.append(keys)
+    return out
+
+
+@pytest.mark.parametrize("n_seq", [1, 257])
+@pytest.mark.parametrize("block_size", [1, 16, 24, 256])
+def test_prefix_hash_edges_match_python_chain(block_size, n_seq):
+    """ops.prefix_hash against the pure-Python CBOR + FNV chain, every
+    sequence compared: array headers of 1, 2 and 3 bytes (block sizes 1/16,
+    24, 256), every token and parent width class, ragged lengths (empty,
+    under one block, exact multiples, a multiple plus a remainder), and
+    257 sequences so a second workgroup runs with one live lane."""
+    import numpy as np
+
+    bs = block_size
+    shapes = [0, bs - 1, 5 * bs, 6 * bs + bs // 2, 8 * bs]
+    lengths = [shapes[(s + 3) % 5] for s in range(n_seq)]
+    rng = np.random.default_rng(1000 * bs + n_seq)
+    seqs, seeds = _prefix_case(lengths, 7 + [1, 16, 24, 256].index(bs), rng)
+    got = _prefix_hash_on_gpu(seqs, seeds, bs)
+    want = _prefix_oracle(seqs, seeds, bs)
+    assert [len(k) for k in got] == [n // bs for n in lengths]
+    for s in range(n_seq):
+        assert got[s] == want[s], f"sequence {s} (seed {seeds[s]:#x})"
+
+
+def test_prefix_hash_all_sequences_shorter_than_a_block():
+    import numpy as np
+
+    lengths = [0, 15, 3, 1, 15]
+    seqs, seeds = _prefix_case(lengths, 0, np.random.default_rng(5))
+    assert _prefix_hash_on_gpu(seqs, seeds, 16) == [[] for _ in lengths]
+
+
+def test_prefix_hash_no_sequences():
+    """n_seq == 0 launches nothing (a grid of zero workgroups is an error
+    in HIP) and returns no key lists."""
+    assert _prefix_hash_on_gpu([], [], 16) == []
+
+
+def test_gpu_block_copier_second_grid_stride_trip():
+    """8448 B x 8 layers x 128 blocks = 1024 tiles: copy_grid gives 2 slices
+    of 256 lanes for 528 vectors, so lanes of slice 0 take a second trip
+    round the grid-stride loop of the raw gather/scatter kernels. Bit-exact
+    against the torch gather, with a guard band behind the slab."""
+    from llm_d_kv_cache_amd.ops import block_copier
+
+    bb, nl, nb = 8448, 8, 128
+    gen = torch.Generator().manual_seed(bb + nl + nb)
+    pages = [torch.randint(0, 256, (2 * nb + 2, bb), generator=gen,
+                           dtype=torch.int64).to(torch.uint8)
+             for _ in range(nl)]
+    ids = list(range(1, 2 * nb, 2))
+    others = [i for i in range(2 * nb + 2) if i not in set(ids)]
+    dev_pages = [p.cuda() for p in pages]
+    copier = block_copier([dev_pages])
+    nbytes = copier.packed_bytes(0, nb)
+    assert nbytes == nb * nl * bb
+    slab = torch.full((nbytes + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    copier.gather(0, ids, slab.data_ptr(), stream)
+    torch.cuda.synchronize()
+    host = slab.cpu()
+    ref = torch.stack([p[ids] for p in pages], dim=1).reshape(-1)
+    assert torch.equal(host[:nbytes], ref)
+    assert (host[nbytes:] == 0xA5).all(), "guard band overwritten"
+    for t in dev_pages:
+        t.zero_()
+    copier.scatter(0, ids, slab.data_ptr(), stream)
+    torch.cuda.synchronize()
+    for t, p in zip(dev_pages, pages):
+        got = t.cpu()
+        assert torch.equal(got[ids], p[ids])
+        assert (got[others] == 0).all()
+
+
 @pytest.mark.parametrize("copy_path", ["staged", "zero_copy"])
 def test_gpu_fp8_serialize_roundtrip(tmp_path, copy_path):
     """CDNA4 fused gather+quantize / dequantize+scatter kernels: round-trip
