@@ -58,8 +58,10 @@ PYBIND11_MODULE(_kvoffload, m) {
                        bool gpu_mode, int device, const std::string& copy_path,
                        const std::string& serialize, size_t host_cache_bytes,
                        const std::string& write_policy, bool direct_io,
-                       int fp8_group_size, bool checksum) {
+                       int fp8_group_size, bool checksum,
+                       const std::string& kv_dtype) {
              EngineConfig cfg;
+             cfg.kv_dtype = parse_kv_dtype(kv_dtype);
              cfg.checksum = checksum;
              cfg.io_threads = io_threads;
              cfg.gpu_blocks_per_file = gpu_blocks_per_file;
@@ -113,7 +115,8 @@ PYBIND11_MODULE(_kvoffload, m) {
            py::arg("device") = 0, py::arg("copy_path") = "staged",
            py::arg("serialize") = "raw", py::arg("host_cache_bytes") = 0,
            py::arg("write_policy") = "through", py::arg("direct_io") = false,
-           py::arg("fp8_group_size") = 128, py::arg("checksum") = false)
+           py::arg("fp8_group_size") = 128, py::arg("checksum") = false,
+           py::arg("kv_dtype") = "bfloat16")
       .def(
           "async_store",
           [](StorageOffloadEngine& e,
@@ -179,7 +182,8 @@ PYBIND11_MODULE(_kvoffload, m) {
 
   py::class_<BlockCopier>(m, "BlockCopier")
       .def(py::init([](std::vector<py::tuple> groups, bool gpu_mode,
-                       int device) {
+                       int device, const std::string& kv_dtype) {
+             const KvDtype dt = parse_kv_dtype(kv_dtype);
              std::vector<GroupDesc> gs;
              for (auto& t : groups) {
                GroupDesc g;
@@ -191,9 +195,11 @@ PYBIND11_MODULE(_kvoffload, m) {
                gs.push_back(std::move(g));
              }
              py::gil_scoped_release rel;
-             return std::make_unique<BlockCopier>(std::move(gs), gpu_mode, device);
+             return std::make_unique<BlockCopier>(std::move(gs), gpu_mode, device,
+                                                  dt);
            }),
-           py::arg("groups"), py::arg("gpu_mode") = false, py::arg("device") = 0)
+           py::arg("groups"), py::arg("gpu_mode") = false, py::arg("device") = 0,
+           py::arg("kv_dtype") = "bfloat16")
       .def("packed_bytes", &BlockCopier::packed_bytes, py::arg("group"),
            py::arg("n_blocks"), py::arg("checksum") = false)
       .def("packed_bytes_fp8", &BlockCopier::packed_bytes_fp8, py::arg("group"),

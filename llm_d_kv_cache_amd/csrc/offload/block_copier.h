@@ -8,6 +8,9 @@
 // selects the record stride payload + 16 (checksum.h) and leaves the footer
 // bytes alone; seal_records() then fills the footers of any such slab and
 // verify_records() checks them.
+//
+// kv_dtype (bf16 by default) is the format of the 16-bit pages; every fp8
+// method of the copier converts with it, the raw ones never look at it.
 #pragma once
 
 #include <mutex>
@@ -21,8 +24,9 @@ namespace kvo {
 
 class BlockCopier {
  public:
-  BlockCopier(std::vector<GroupDesc> groups, bool gpu_mode, int device)
-      : groups_(std::move(groups)), gpu_mode_(gpu_mode) {
+  BlockCopier(std::vector<GroupDesc> groups, bool gpu_mode, int device,
+              KvDtype kv_dtype = KvDtype::kBf16)
+      : groups_(std::move(groups)), gpu_mode_(gpu_mode), kv_dtype_(kv_dtype) {
     if (gpu_mode_) {
       KVO_HIP_CHECK(hipSetDevice(device));
       for (auto& g : groups_) {
@@ -133,7 +137,8 @@ class BlockCopier {
         dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
         g.block_bytes, ids.data(), static_cast<int>(ids.size()), nullptr,
         static_cast<uint8_t*>(dst), static_cast<float*>(scratch),
-        reinterpret_cast<hipStream_t>(stream), footer(checksum));
+        reinterpret_cast<hipStream_t>(stream), footer(checksum),
+        static_cast<int>(kv_dtype_));
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
@@ -153,7 +158,7 @@ class BlockCopier {
         dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
         g.block_bytes, ids.data(), static_cast<int>(ids.size()), nullptr,
         static_cast<const uint8_t*>(src), reinterpret_cast<hipStream_t>(stream),
-        footer(checksum));
+        footer(checksum), static_cast<int>(kv_dtype_));
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
@@ -180,7 +185,7 @@ class BlockCopier {
     if (!gpu_mode_) {
       StorageOffloadEngine::host_fp8_group_copy(
           g, ids, static_cast<uint8_t*>(dst), group_size, /*quantize=*/true,
-          footer(checksum));
+          footer(checksum), kv_dtype_);
       return;
     }
     hipError_t err = kvc_launch_gather_fp8_group(
@@ -188,7 +193,8 @@ class BlockCopier {
         dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
         g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
         nullptr, static_cast<uint8_t*>(dst),
-        reinterpret_cast<hipStream_t>(stream), footer(checksum));
+        reinterpret_cast<hipStream_t>(stream), footer(checksum),
+        static_cast<int>(kv_dtype_));
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
@@ -202,7 +208,7 @@ class BlockCopier {
     if (!gpu_mode_) {
       StorageOffloadEngine::host_fp8_group_copy(
           g, ids, const_cast<uint8_t*>(static_cast<const uint8_t*>(src)),
-          group_size, /*quantize=*/false, footer(checksum));
+          group_size, /*quantize=*/false, footer(checksum), kv_dtype_);
       return;
     }
     hipError_t err = kvc_launch_scatter_fp8_group(
@@ -210,7 +216,8 @@ class BlockCopier {
         dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
         g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
         nullptr, static_cast<const uint8_t*>(src),
-        reinterpret_cast<hipStream_t>(stream), footer(checksum));
+        reinterpret_cast<hipStream_t>(stream), footer(checksum),
+        static_cast<int>(kv_dtype_));
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
@@ -328,11 +335,13 @@ class BlockCopier {
   void host_fp8(const GroupDesc& g, const std::vector<int32_t>& ids,
                 uint8_t* packed, bool quantize, size_t footer) const {
     // software codec shared with the engine's host mode
-    StorageOffloadEngine::host_fp8_copy(g, ids, packed, quantize, footer);
+    StorageOffloadEngine::host_fp8_copy(g, ids, packed, quantize, footer,
+                                        kv_dtype_);
   }
 
   std::vector<GroupDesc> groups_;
   bool gpu_mode_;
+  KvDtype kv_dtype_;
   std::vector<void**> dev_layer_ptrs_;
   std::vector<uint64_t*> dev_layer_strides_;
   std::mutex csum_mu_;

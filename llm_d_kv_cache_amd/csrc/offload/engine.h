@@ -39,6 +39,8 @@
 // pointer (ids_dev != nullptr) for bigger transfers — no kernel-side
 // blocks-per-file ceiling. The trailing uint32_t is the footer bytes every
 // record carries behind its payload: 0 (dense layout) or 16 (checksums).
+// The fp8 launchers end with the page format, a KvDtype as int; any other
+// value returns hipErrorInvalidValue.
 extern "C" hipError_t kvc_launch_gather(const void* const*, const uint64_t*, int,
                                         uint64_t, const int32_t*, int,
                                         const int32_t*, uint8_t*, hipStream_t,
@@ -50,21 +52,21 @@ extern "C" hipError_t kvc_launch_scatter(const void* const*, const uint64_t*, in
 extern "C" hipError_t kvc_launch_gather_fp8(const void* const*, const uint64_t*,
                                             int, uint64_t, const int32_t*, int,
                                             const int32_t*, uint8_t*,
-                                            hipStream_t, uint32_t);
+                                            hipStream_t, uint32_t, int);
 extern "C" hipError_t kvc_launch_gather_fp8_split(
     const void* const*, const uint64_t*, int, uint64_t, const int32_t*, int,
-    const int32_t*, uint8_t*, float*, hipStream_t, uint32_t);
+    const int32_t*, uint8_t*, float*, hipStream_t, uint32_t, int);
 extern "C" hipError_t kvc_launch_scatter_fp8(const void* const*, const uint64_t*,
                                              int, uint64_t, const int32_t*, int,
                                              const int32_t*, const uint8_t*,
-                                             hipStream_t, uint32_t);
+                                             hipStream_t, uint32_t, int);
 // group-scaled fp8: the int after block_bytes is the group size in elements
 extern "C" hipError_t kvc_launch_gather_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
-    int, const int32_t*, uint8_t*, hipStream_t, uint32_t);
+    int, const int32_t*, uint8_t*, hipStream_t, uint32_t, int);
 extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
-    int, const int32_t*, const uint8_t*, hipStream_t, uint32_t);
+    int, const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
 // Record checksums (checksum.h has the format and the host twin). slab holds
 // `tiles` records of payload_bytes + 16; scratch is
 // kvc_checksum_scratch_bytes(tiles) of 8-byte aligned device memory; result
@@ -95,12 +97,25 @@ inline size_t pipeline_chunk(size_t bytes) {
 
 enum class CopyPath { kStaged, kZeroCopy, kHostMemcpy };
 
-// Payload serialization: raw bytes, or fp8 e4m3fn quantization of bf16
-// pages (halves wire + storage bytes; one f32 scale per (block, layer)
+// Payload serialization: raw bytes, or fp8 e4m3fn quantization of 16-bit
+// float pages (halves wire + storage bytes; one f32 scale per (block, layer)
 // tile appended to each tile record). kFp8E4M3Group scales every
 // fp8_group_size-element run on its own (users set it to head_dim): the
 // record is [ n fp8 | n/G f32 scales ], n = block_bytes/2.
 enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group };
+
+// Format of the 16-bit KV pages the fp8 modes read on store and write on
+// load (raw copies never look at it). The records are format-free; only the
+// page <-> f32 conversions differ. The values are the kv_dtype argument of
+// the fp8 launchers in kernels.hip.
+enum class KvDtype : int { kBf16 = 0, kFp16 = 1 };
+
+inline KvDtype parse_kv_dtype(const std::string& s) {
+  if (s == "bfloat16") return KvDtype::kBf16;
+  if (s == "float16") return KvDtype::kFp16;
+  throw std::invalid_argument("kv_dtype must be bfloat16|float16 (got '" + s +
+                              "')");
+}
 
 inline bool fp8_group_size_ok(int g) {
   return g == 64 || g == 128 || g == 256 || g == 512;
@@ -144,6 +159,8 @@ struct EngineConfig {
   // page is written. Files with and without footers must not share a
   // directory: tag the FileMapper dtype with "+ck" (docs/configuration.md).
   bool checksum = false;
+  // Page format of the KV tensors; consulted only by the fp8 modes.
+  KvDtype kv_dtype = KvDtype::kBf16;
 };
 
 struct FileTransfer {
@@ -759,7 +776,7 @@ class StorageOffloadEngine {
             const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
             dev_layer_strides_[ft.group], nl, g.block_bytes,
             cfg_.fp8_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
-            ctx.stream, footer_bytes());
+            ctx.stream, footer_bytes(), static_cast<int>(cfg_.kv_dtype));
       } else if (cfg_.serialize == Serialize::kFp8E4M3) {
         if (cfg_.copy_path == CopyPath::kStaged) {
           // split amax+quantize (chip-filling); the partial-max scratch
@@ -773,7 +790,7 @@ class StorageOffloadEngine {
               const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
               dev_layer_strides_[ft.group], nl, g.block_bytes,
               ft.block_ids.data(), nb, ids_dev, kernel_dst, scratch,
-              ctx.stream, footer_bytes());
+              ctx.stream, footer_bytes(), static_cast<int>(cfg_.kv_dtype));
         } else {
           // zero-copy writes pinned host directly: atomics over PCIe are
           // pathological, keep the fused single-workgroup variant
@@ -781,7 +798,7 @@ class StorageOffloadEngine {
               const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
               dev_layer_strides_[ft.group], nl, g.block_bytes,
               ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream,
-              footer_bytes());
+              footer_bytes(), static_cast<int>(cfg_.kv_dtype));
         }
       } else {
         err = kvc_launch_gather(
@@ -992,11 +1009,12 @@ class StorageOffloadEngine {
         return kvc_launch_scatter_fp8_group(
             ptrs, strides, nl, g.block_bytes, cfg_.fp8_group_size,
             ft.block_ids.data(), nb, ids_dev, src, ctx.stream,
-            footer_bytes());
+            footer_bytes(), static_cast<int>(cfg_.kv_dtype));
       case Serialize::kFp8E4M3:
         return kvc_launch_scatter_fp8(ptrs, strides, nl, g.block_bytes,
                                       ft.block_ids.data(), nb, ids_dev, src,
-                                      ctx.stream, footer_bytes());
+                                      ctx.stream, footer_bytes(),
+                                      static_cast<int>(cfg_.kv_dtype));
       default:
         return kvc_launch_scatter(ptrs, strides, nl, g.block_bytes,
                                   ft.block_ids.data(), nb, ids_dev, src,
@@ -1184,9 +1202,10 @@ class StorageOffloadEngine {
                              static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
         uint8_t* out = dst + (bi * nl + l) * rec;
         if (cfg_.serialize == Serialize::kFp8E4M3)
-          fp8_quantize_tile(src, g.block_bytes, out);
+          fp8_quantize_tile(src, g.block_bytes, out, cfg_.kv_dtype);
         else if (cfg_.serialize == Serialize::kFp8E4M3Group)
-          fp8_group_quantize_tile(src, g.block_bytes, cfg_.fp8_group_size, out);
+          fp8_group_quantize_tile(src, g.block_bytes, cfg_.fp8_group_size, out,
+                                  cfg_.kv_dtype);
         else
           std::memcpy(out, src, g.block_bytes);
       }
@@ -1203,9 +1222,10 @@ class StorageOffloadEngine {
                        static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
         const uint8_t* in = src + (bi * nl + l) * rec;
         if (cfg_.serialize == Serialize::kFp8E4M3)
-          fp8_dequantize_tile(in, g.block_bytes, dst);
+          fp8_dequantize_tile(in, g.block_bytes, dst, cfg_.kv_dtype);
         else if (cfg_.serialize == Serialize::kFp8E4M3Group)
-          fp8_group_dequantize_tile(in, g.block_bytes, cfg_.fp8_group_size, dst);
+          fp8_group_dequantize_tile(in, g.block_bytes, cfg_.fp8_group_size, dst,
+                                    cfg_.kv_dtype);
         else
           std::memcpy(dst, in, g.block_bytes);
       }
@@ -1214,18 +1234,69 @@ class StorageOffloadEngine {
 
   // ---- software fp8 e4m3fn (host-mode twin of the CDNA4 kernels) -----------
 
-  static float bf16_to_f32(uint16_t u) {
-    uint32_t w = static_cast<uint32_t>(u) << 16;
-    float f;
-    std::memcpy(&f, &w, 4);
-    return f;
-  }
-  static uint16_t f32_to_bf16(float f) {
-    uint32_t w;
-    std::memcpy(&w, &f, 4);
-    uint32_t rounding = 0x7fff + ((w >> 16) & 1);
-    return static_cast<uint16_t>((w + rounding) >> 16);
-  }
+  // Host twins of the kernels' page traits.
+  struct PageBf16 {
+    static float to_f32(uint16_t u) {
+      uint32_t w = static_cast<uint32_t>(u) << 16;
+      float f;
+      std::memcpy(&f, &w, 4);
+      return f;
+    }
+    static uint16_t from_f32(float f) {
+      uint32_t w;
+      std::memcpy(&w, &f, 4);
+      uint32_t rounding = 0x7fff + ((w >> 16) & 1);
+      return static_cast<uint16_t>((w + rounding) >> 16);
+    }
+  };
+  // Portable IEEE binary16 bit conversions (no F16C): exact widening with
+  // subnormals, and round-to-nearest-even narrowing that produces
+  // subnormals and overflows to infinity from 65520 up.
+  struct PageFp16 {
+    static float to_f32(uint16_t u) {
+      const uint32_t sign = static_cast<uint32_t>(u & 0x8000u) << 16;
+      const uint32_t em = u & 0x7fffu;
+      uint32_t w;
+      float f;
+      if (em >= 0x7c00u) {  // inf / NaN
+        w = 0x7f800000u | ((em & 0x3ffu) << 13);
+      } else if (em < 0x0400u) {  // zero / subnormal: em * 2^-24, exact
+        f = static_cast<float>(em) * 5.9604644775390625e-08f;
+        std::memcpy(&w, &f, 4);
+      } else {
+        w = (em << 13) + ((127u - 15u) << 23);
+      }
+      w |= sign;
+      std::memcpy(&f, &w, 4);
+      return f;
+    }
+    static uint16_t from_f32(float f) {
+      uint32_t w;
+      std::memcpy(&w, &f, 4);
+      const uint32_t sign = (w >> 16) & 0x8000u;
+      w &= 0x7fffffffu;
+      uint32_t o;
+      if (w >= ((127u + 16u) << 23)) {  // >= 65536, inf, NaN
+        o = w > 0x7f800000u ? 0x7e00u : 0x7c00u;
+      } else if (w < (113u << 23)) {
+        // below the min normal 2^-14: the ulp of [0.5, 1) is 2^-24, the fp16
+        // subnormal step, so adding 0.5 leaves RNE(|f| / 2^-24) in the low
+        // mantissa bits (1024 = the encoding of 2^-14 itself)
+        float a;
+        std::memcpy(&a, &w, 4);
+        a += 0.5f;
+        std::memcpy(&o, &a, 4);
+        o -= 0x3f000000u;
+      } else {
+        // rebias, then round the 13 dropped bits to even; a carry runs into
+        // the exponent by itself (65520 and up become 0x7c00)
+        const uint32_t odd = (w >> 13) & 1u;
+        w += 0xc8000fffu + odd;  // ((15 - 127) << 23) + 0xfff, mod 2^32
+        o = w >> 13;
+      }
+      return static_cast<uint16_t>(sign | o);
+    }
+  };
   // Round-to-nearest-even OCP e4m3fn encoder (1s 4e 3m, bias 7, max 448,
   // no inf) of both fp8 modes: the CDNA4 cvt_pk_fp8_f32 rounding, ties to
   // even, saturating at +-448. Finite inputs only (fp8_quantize_tile guards
@@ -1272,7 +1343,8 @@ class StorageOffloadEngine {
   // Shared software fp8 path (BlockCopier's host mode reuses it).
   // footer: bytes every record carries behind its payload (0 or 16).
   static void host_fp8_copy(const GroupDesc& g, const std::vector<int32_t>& ids,
-                            uint8_t* packed, bool quantize, size_t footer = 0) {
+                            uint8_t* packed, bool quantize, size_t footer = 0,
+                            KvDtype kv_dtype = KvDtype::kBf16) {
     const size_t nl = g.layer_ptrs.size();
     const size_t rec = g.block_bytes / 2 + 4 + footer;
     for (size_t bi = 0; bi < ids.size(); ++bi) {
@@ -1281,9 +1353,9 @@ class StorageOffloadEngine {
                         static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
         uint8_t* slab = packed + (bi * nl + l) * rec;
         if (quantize)
-          fp8_quantize_tile(page, g.block_bytes, slab);
+          fp8_quantize_tile(page, g.block_bytes, slab, kv_dtype);
         else
-          fp8_dequantize_tile(slab, g.block_bytes, page);
+          fp8_dequantize_tile(slab, g.block_bytes, page, kv_dtype);
       }
     }
   }
@@ -1298,7 +1370,8 @@ class StorageOffloadEngine {
   static void host_fp8_group_copy(const GroupDesc& g,
                                   const std::vector<int32_t>& ids,
                                   uint8_t* packed, int group_size,
-                                  bool quantize, size_t footer = 0) {
+                                  bool quantize, size_t footer = 0,
+                                  KvDtype kv_dtype = KvDtype::kBf16) {
     const size_t nl = g.layer_ptrs.size();
     const size_t rec =
         fp8_group_record_bytes(g.block_bytes, group_size) + footer;
@@ -1308,9 +1381,11 @@ class StorageOffloadEngine {
                         static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
         uint8_t* slab = packed + (bi * nl + l) * rec;
         if (quantize)
-          fp8_group_quantize_tile(page, g.block_bytes, group_size, slab);
+          fp8_group_quantize_tile(page, g.block_bytes, group_size, slab,
+                                  kv_dtype);
         else
-          fp8_group_dequantize_tile(slab, g.block_bytes, group_size, page);
+          fp8_group_dequantize_tile(slab, g.block_bytes, group_size, page,
+                                    kv_dtype);
       }
     }
   }
@@ -1318,7 +1393,8 @@ class StorageOffloadEngine {
   private:
   // Record starts are only 4-byte aligned and scales follow n payload
   // bytes: scales move through memcpy.
-  static void fp8_group_quantize_tile(const uint8_t* src, size_t block_bytes,
+  template <typename T>
+  static void fp8_group_quantize_tile_t(const uint8_t* src, size_t block_bytes,
                                       int group_size, uint8_t* out) {
     const size_t n = block_bytes / 2;
     const size_t G = static_cast<size_t>(group_size);
@@ -1327,17 +1403,18 @@ class StorageOffloadEngine {
       const uint16_t* x = in + gi * G;
       float amax = 0.0f;
       for (size_t i = 0; i < G; ++i)
-        amax = std::max(amax, std::abs(bf16_to_f32(x[i])));
+        amax = std::max(amax, std::abs(T::to_f32(x[i])));
       if (amax <= 0.0f) amax = 1.0f;
       const float scale = amax / 448.0f;
       const float inv = 448.0f / amax;
       for (size_t i = 0; i < G; ++i)
-        out[gi * G + i] = f32_to_fp8_rne(bf16_to_f32(x[i]) * inv);
+        out[gi * G + i] = f32_to_fp8_rne(T::to_f32(x[i]) * inv);
       std::memcpy(out + n + 4 * gi, &scale, 4);
     }
   }
 
-  static void fp8_group_dequantize_tile(const uint8_t* in, size_t block_bytes,
+  template <typename T>
+  static void fp8_group_dequantize_tile_t(const uint8_t* in, size_t block_bytes,
                                         int group_size, uint8_t* dst) {
     const size_t n = block_bytes / 2;
     const size_t G = static_cast<size_t>(group_size);
@@ -1346,22 +1423,23 @@ class StorageOffloadEngine {
       float scale;
       std::memcpy(&scale, in + n + 4 * gi, 4);
       for (size_t i = 0; i < G; ++i)
-        out[gi * G + i] = f32_to_bf16(fp8_to_f32(in[gi * G + i]) * scale);
+        out[gi * G + i] = T::from_f32(fp8_to_f32(in[gi * G + i]) * scale);
     }
   }
 
-  static void fp8_quantize_tile(const uint8_t* src, size_t block_bytes,
+  template <typename T>
+  static void fp8_quantize_tile_t(const uint8_t* src, size_t block_bytes,
                          uint8_t* out) {
     const size_t n = block_bytes / 2;
     const uint16_t* in = reinterpret_cast<const uint16_t*>(src);
     float amax = 0.0f;
     for (size_t i = 0; i < n; ++i)
-      amax = std::max(amax, std::abs(bf16_to_f32(in[i])));
+      amax = std::max(amax, std::abs(T::to_f32(in[i])));
     if (amax <= 0.0f) amax = 1.0f;
     float scale = amax / 448.0f;
     float inv = 448.0f / amax;
     for (size_t i = 0; i < n; ++i) {
-      const float x = bf16_to_f32(in[i]) * inv;
+      const float x = T::to_f32(in[i]) * inv;
       // a NaN never enters amax (std::max keeps the other operand) and is
       // stored as the e4m3fn NaN code, so it loads as NaN
       out[i] = x != x ? 0x7f : f32_to_fp8_rne(x);
@@ -1369,14 +1447,47 @@ class StorageOffloadEngine {
     std::memcpy(out + n, &scale, 4);
   }
 
-  static void fp8_dequantize_tile(const uint8_t* in, size_t block_bytes,
+  template <typename T>
+  static void fp8_dequantize_tile_t(const uint8_t* in, size_t block_bytes,
                            uint8_t* dst) {
     const size_t n = block_bytes / 2;
     float scale;
     std::memcpy(&scale, in + n, 4);
     uint16_t* out = reinterpret_cast<uint16_t*>(dst);
     for (size_t i = 0; i < n; ++i)
-      out[i] = f32_to_bf16(fp8_to_f32(in[i]) * scale);
+      out[i] = T::from_f32(fp8_to_f32(in[i]) * scale);
+  }
+
+  // Runtime page format -> the templated codec above.
+  static void fp8_group_quantize_tile(const uint8_t* src, size_t block_bytes,
+                                      int group_size, uint8_t* out,
+                                      KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_group_quantize_tile_t<PageFp16>(src, block_bytes, group_size, out);
+    else
+      fp8_group_quantize_tile_t<PageBf16>(src, block_bytes, group_size, out);
+  }
+  static void fp8_group_dequantize_tile(const uint8_t* in, size_t block_bytes,
+                                        int group_size, uint8_t* dst,
+                                        KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_group_dequantize_tile_t<PageFp16>(in, block_bytes, group_size, dst);
+    else
+      fp8_group_dequantize_tile_t<PageBf16>(in, block_bytes, group_size, dst);
+  }
+  static void fp8_quantize_tile(const uint8_t* src, size_t block_bytes,
+                                uint8_t* out, KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_quantize_tile_t<PageFp16>(src, block_bytes, out);
+    else
+      fp8_quantize_tile_t<PageBf16>(src, block_bytes, out);
+  }
+  static void fp8_dequantize_tile(const uint8_t* in, size_t block_bytes,
+                                  uint8_t* dst, KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_dequantize_tile_t<PageFp16>(in, block_bytes, dst);
+    else
+      fp8_dequantize_tile_t<PageBf16>(in, block_bytes, dst);
   }
 
   EngineConfig cfg_;

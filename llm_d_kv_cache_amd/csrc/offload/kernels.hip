@@ -217,8 +217,9 @@ extern "C" hipError_t kvc_launch_prefix_hash(
 
 namespace kvo {
 // ---- fp8 (OCP e4m3fn) serialization ----------------------------------------
-// Fused gather+quantize on store and dequantize+scatter on load: bf16 KV
-// pages are serialized as fp8 with one f32 scale per (block, layer) tile,
+// Fused gather+quantize on store and dequantize+scatter on load: 16-bit KV
+// pages (bf16 or fp16, a template parameter — see the page traits below)
+// are serialized as fp8 with one f32 scale per (block, layer) tile,
 // halving PCIe and storage bytes. Packed slab layout is self-contained per
 // tile record (so partial-span tail-seek loads work):
 //   [ tile fp8 payload (block_bytes/2) | f32 scale ] x tiles
@@ -228,17 +229,64 @@ namespace kvo {
 
 namespace {
 
-__device__ __forceinline__ float bf16_to_f32(uint16_t u) {
-  uint32_t w = static_cast<uint32_t>(u) << 16;
-  return __uint_as_float(w);
-}
+// Page formats. Every fp8 kernel below is a template on one of these
+// traits: the record layout and all f32 arithmetic are format-free, only
+// the page -> f32 conversion on store and the f32 -> page rounding on load
+// differ. The launchers pick the trait from their trailing kv_dtype
+// argument (kKvBf16 = 0 keeps the bytes this file has always produced).
+struct PageBf16 {
+  static __device__ __forceinline__ float to_f32(uint16_t u) {
+    uint32_t w = static_cast<uint32_t>(u) << 16;
+    return __uint_as_float(w);
+  }
+  static __device__ __forceinline__ uint16_t from_f32(float f) {
+    uint32_t w = __float_as_uint(f);
+    // round-to-nearest-even
+    uint32_t rounding = 0x7fff + ((w >> 16) & 1);
+    return static_cast<uint16_t>((w + rounding) >> 16);
+  }
+};
 
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  uint32_t w = __float_as_uint(f);
-  // round-to-nearest-even
-  uint32_t rounding = 0x7fff + ((w >> 16) & 1);
-  return static_cast<uint16_t>((w + rounding) >> 16);
-}
+struct PageFp16 {
+  // exact, fp16 subnormals included (v_cvt_f32_f16)
+  static __device__ __forceinline__ float to_f32(uint16_t u) {
+    return static_cast<float>(__builtin_bit_cast(_Float16, u));
+  }
+  // Round-to-nearest-even cast that keeps fp16 subnormals; NOT the packed
+  // cvt_pkrtz builtin, which rounds toward zero. At the call sites the
+  // argument is the product f32(q) * scale. As written here hipcc -O3
+  // emits v_pk_mul_f32 + v_cvt_pk_f16_f32 (mode-RNE): the spec's two
+  // roundings, f32 then fp16. The compiler is free to fold product and
+  // cast into one v_fma_mixlo_f16 instead (it does for the scalar form of
+  // this expression, and __fmul_rn does not stop it): a single rounding of
+  // the exact product. For every record our encoders write the two agree
+  // bit for bit: over all e4m3 codes and every scale = amax/448 with an
+  // fp16-representable amax, (m/7) * amax never lies within f32 rounding
+  // of an fp16 tie (checked exhaustively on the CPU, 50.4 M pairs), so
+  // either form is acceptable and nothing here forces one.
+  static __device__ __forceinline__ uint16_t from_f32(float f) {
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
+  }
+};
+
+constexpr int kKvBf16 = 0;
+constexpr int kKvFp16 = 1;
+
+// Runs `...` with T bound to the page trait of kv_dtype; an unknown format
+// makes the enclosing launcher return hipErrorInvalidValue.
+#define KVC_WITH_PAGE_TYPE(kv_dtype, ...)          \
+  switch (kv_dtype) {                              \
+    case kKvBf16: {                                \
+      using T = PageBf16;                          \
+      __VA_ARGS__;                                 \
+    } break;                                       \
+    case kKvFp16: {                                \
+      using T = PageFp16;                          \
+      __VA_ARGS__;                                 \
+    } break;                                       \
+    default:                                       \
+      return hipErrorInvalidValue;                 \
+  }
 
 constexpr float kFp8Max = 448.0f;  // e4m3fn max normal
 
@@ -254,6 +302,7 @@ __device__ __forceinline__ float fp8_e4m3_to_f32(uint8_t b) {
 // split's win). Pass 2 reduces the <=slices partials per tile at its
 // head. Grid: x = tile, y = slices per tile; both passes use the SAME
 // grid.
+template <typename T>
 __global__ __launch_bounds__(256) void kvc_fp8_amax(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -276,8 +325,8 @@ __global__ __launch_bounds__(256) void kvc_fp8_amax(
     const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      amax = fmaxf(amax, fabsf(bf16_to_f32(static_cast<uint16_t>(dw[j]))));
-      amax = fmaxf(amax, fabsf(bf16_to_f32(static_cast<uint16_t>(dw[j] >> 16))));
+      amax = fmaxf(amax, fabsf(T::to_f32(static_cast<uint16_t>(dw[j]))));
+      amax = fmaxf(amax, fabsf(T::to_f32(static_cast<uint16_t>(dw[j] >> 16))));
     }
   }
   __shared__ float lds_max[4];
@@ -294,6 +343,7 @@ __global__ __launch_bounds__(256) void kvc_fp8_amax(
 // Pass 2: quantize with full chip parallelism (grid-stride slices per
 // tile), reading the tile amax from scales[] and rewriting it as the
 // actual scale in the output record.
+template <typename T>
 __global__ __launch_bounds__(256) void kvc_fp8_quant(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -327,17 +377,17 @@ __global__ __launch_bounds__(256) void kvc_fp8_quant(
     uint2 out;
     uint32_t lo = 0, hi = 0;
     lo = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[0])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[0] >> 16)) * inv_scale, lo, 0);
+        T::to_f32(static_cast<uint16_t>(dw[0])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[0] >> 16)) * inv_scale, lo, 0);
     lo = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[1])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[1] >> 16)) * inv_scale, lo, 1);
+        T::to_f32(static_cast<uint16_t>(dw[1])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[1] >> 16)) * inv_scale, lo, 1);
     hi = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[2])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[2] >> 16)) * inv_scale, hi, 0);
+        T::to_f32(static_cast<uint16_t>(dw[2])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[2] >> 16)) * inv_scale, hi, 0);
     hi = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[3])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[3] >> 16)) * inv_scale, hi, 1);
+        T::to_f32(static_cast<uint16_t>(dw[3])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[3] >> 16)) * inv_scale, hi, 1);
     out.x = lo;
     out.y = hi;
     vout[v] = out;
@@ -347,6 +397,7 @@ __global__ __launch_bounds__(256) void kvc_fp8_quant(
 // Legacy single-workgroup-per-tile fused variant: the zero-copy path keeps
 // it (its destination is device-mapped pinned host memory, where the
 // split's scratch round trip would cross PCIe).
+template <typename T>
 __global__ __launch_bounds__(256) void kvc_gather_fp8(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -356,7 +407,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
   const uint32_t tile = blockIdx.x;
   const int l = tile % num_layers;
   const int bi = tile / num_layers;
-  const uint64_t n_elems = block_bytes / 2;  // bf16 elements per tile
+  const uint64_t n_elems = block_bytes / 2;  // 16-bit elements per tile
   const uint64_t record = n_elems + 4 + footer_bytes;  // payload + f32 scale
   const uint16_t* __restrict__ src = reinterpret_cast<const uint16_t*>(
       static_cast<const uint8_t*>(layer_ptrs[l]) +
@@ -365,7 +416,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
   float* __restrict__ scale_out =
       reinterpret_cast<float*>(payload + n_elems);
 
-  // pass 1: tile amax — 16 B/lane vectorized (8 bf16 per load)
+  // pass 1: tile amax — 16 B/lane vectorized (8 values per load)
   __shared__ float lds_max[4];
   const uint4* __restrict__ vsrc = reinterpret_cast<const uint4*>(src);
   const uint64_t nvec = n_elems / 8;  // block_bytes % 16 == 0 host-checked
@@ -375,8 +426,8 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
     const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      amax = fmaxf(amax, fabsf(bf16_to_f32(static_cast<uint16_t>(dw[j]))));
-      amax = fmaxf(amax, fabsf(bf16_to_f32(static_cast<uint16_t>(dw[j] >> 16))));
+      amax = fmaxf(amax, fabsf(T::to_f32(static_cast<uint16_t>(dw[j]))));
+      amax = fmaxf(amax, fabsf(T::to_f32(static_cast<uint16_t>(dw[j] >> 16))));
     }
   }
   for (int off = 32; off > 0; off >>= 1)
@@ -391,7 +442,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
   __syncthreads();
   const float inv_scale = kFp8Max / lds_max[0];
 
-  // pass 2: quantize — read 8 bf16, emit 8 fp8 as one dwordx2 store
+  // pass 2: quantize — read 8 values, emit 8 fp8 as one dwordx2 store
   uint2* __restrict__ vout = reinterpret_cast<uint2*>(payload);
   for (uint64_t v = threadIdx.x; v < nvec; v += blockDim.x) {
     uint4 w = vsrc[v];
@@ -400,17 +451,17 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
     uint32_t lo = 0, hi = 0;
     // word_sel must be an immediate: unrolled by hand
     lo = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[0])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[0] >> 16)) * inv_scale, lo, 0);
+        T::to_f32(static_cast<uint16_t>(dw[0])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[0] >> 16)) * inv_scale, lo, 0);
     lo = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[1])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[1] >> 16)) * inv_scale, lo, 1);
+        T::to_f32(static_cast<uint16_t>(dw[1])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[1] >> 16)) * inv_scale, lo, 1);
     hi = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[2])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[2] >> 16)) * inv_scale, hi, 0);
+        T::to_f32(static_cast<uint16_t>(dw[2])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[2] >> 16)) * inv_scale, hi, 0);
     hi = __builtin_amdgcn_cvt_pk_fp8_f32(
-        bf16_to_f32(static_cast<uint16_t>(dw[3])) * inv_scale,
-        bf16_to_f32(static_cast<uint16_t>(dw[3] >> 16)) * inv_scale, hi, 1);
+        T::to_f32(static_cast<uint16_t>(dw[3])) * inv_scale,
+        T::to_f32(static_cast<uint16_t>(dw[3] >> 16)) * inv_scale, hi, 1);
     out.x = lo;
     out.y = hi;
     vout[v] = out;
@@ -421,6 +472,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8(
 // dequant needs no cross-workgroup reduction, the per-tile scale is read
 // from the record tail by every slice (uniform L2-hit load). Replaces the
 // one-workgroup-per-tile legacy that left the chip 25+% idle on loads.
+template <typename T>
 __global__ __launch_bounds__(256) void kvc_scatter_fp8(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -439,7 +491,7 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8(
       src + static_cast<uint64_t>(tile) * record;
   const float scale =
       *reinterpret_cast<const float*>(payload + n_elems);
-  // read 8 fp8 as one dwordx2, write 8 bf16 as one dwordx4
+  // read 8 fp8 as one dwordx2, write 8 page values as one dwordx4
   const uint2* __restrict__ vin = reinterpret_cast<const uint2*>(payload);
   uint4* __restrict__ vout = reinterpret_cast<uint4*>(out);
   const uint64_t nvec = n_elems / 8;
@@ -454,8 +506,8 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8(
     for (int j = 0; j < 4; ++j) {
       uint8_t b0 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16));
       uint8_t b1 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16 + 8));
-      uint16_t h0 = f32_to_bf16(fp8_e4m3_to_f32(b0) * scale);
-      uint16_t h1 = f32_to_bf16(fp8_e4m3_to_f32(b1) * scale);
+      uint16_t h0 = T::from_f32(fp8_e4m3_to_f32(b0) * scale);
+      uint16_t h1 = T::from_f32(fp8_e4m3_to_f32(b1) * scale);
       od[j] = static_cast<uint32_t>(h0) | (static_cast<uint32_t>(h1) << 16);
     }
     vout[v] = o;
@@ -466,16 +518,18 @@ extern "C" hipError_t kvc_launch_gather_fp8(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream,
-    uint32_t footer_bytes) {
+    uint32_t footer_bytes, int kv_dtype) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
     for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
   }
   int tiles = num_blocks * num_layers;
-  hipLaunchKernelGGL(kvc_gather_fp8, dim3(tiles), dim3(256), 0, stream,
-                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, dst, footer_bytes);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_gather_fp8<T>, dim3(tiles), dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, dst, footer_bytes));
   return hipGetLastError();
 }
 
@@ -485,7 +539,8 @@ extern "C" hipError_t kvc_launch_gather_fp8_split(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, uint8_t* dst,
-    float* scales_scratch, hipStream_t stream, uint32_t footer_bytes) {
+    float* scales_scratch, hipStream_t stream, uint32_t footer_bytes,
+    int kv_dtype) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -493,12 +548,15 @@ extern "C" hipError_t kvc_launch_gather_fp8_split(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
-  hipLaunchKernelGGL(kvc_fp8_amax, grid, dim3(256), 0, stream,
-                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, scales_scratch);
-  hipLaunchKernelGGL(kvc_fp8_quant, grid, dim3(256), 0, stream,
-                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, scales_scratch, dst, footer_bytes);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_fp8_amax<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, scales_scratch);
+      hipLaunchKernelGGL(kvc_fp8_quant<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, scales_scratch, dst,
+                         footer_bytes));
   return hipGetLastError();
 }
 
@@ -506,7 +564,7 @@ extern "C" hipError_t kvc_launch_scatter_fp8(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, const int32_t* block_ids,
     int num_blocks, const int32_t* ids_dev, const uint8_t* src,
-    hipStream_t stream, uint32_t footer_bytes) {
+    hipStream_t stream, uint32_t footer_bytes, int kv_dtype) {
   BlockList bl;
   if (ids_dev == nullptr) {
     if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
@@ -514,30 +572,33 @@ extern "C" hipError_t kvc_launch_scatter_fp8(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
-  hipLaunchKernelGGL(kvc_scatter_fp8, grid, dim3(256), 0, stream,
-                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     bl, ids_dev, src, footer_bytes);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_scatter_fp8<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, src, footer_bytes));
   return hipGetLastError();
 }
 
 // ---- group-scaled fp8 (one f32 scale per G-element run) ---------------------
 // serialize="fp8_e4m3_group": a tile record is
 //   [ n fp8 bytes | n/G f32 scales ],  n = block_bytes/2,  n % G == 0
-// with G in {64, 128, 256, 512}. At 8 bf16 per lane a group is G/8 = 8..64
+// with G in {64, 128, 256, 512}. At 8 page values per lane a group is G/8 = 8..64
 // consecutive lanes of one wave, so the group amax is a log2(G/8)-step xor
 // butterfly inside the wave: ONE pass over the source, no scratch slab, no
 // LDS, no second launch — which also makes it the right kernel for the
 // zero-copy path (nothing but the record itself crosses PCIe).
 //
 // Per group, all f32: amax = max|x| (0 -> 1), scale = amax/448 (stored),
-// q = RNE_e4m3fn(x * (448/amax)); load: y = bf16_RNE(f32(q) * scale).
+// q = RNE_e4m3fn(x * (448/amax)); load: y = T_RNE(f32(q) * scale), T the
+// page type.
 
 // kLanes = G/8 lanes per group. The grid-stride loop runs on a WAVE-UNIFORM
 // base with a guarded body, so every lane of the wave reaches every shuffle
 // even when n/8 is not a multiple of 64; groups are kLanes-aligned runs of
 // v and n % G == 0, so a group is either wholly inside the tile or wholly
 // past its end, and the xor butterfly (offsets < kLanes) never leaves it.
-template <int kLanes>
+template <int kLanes, typename T>
 __global__ __launch_bounds__(256) void kvc_gather_fp8_group(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -573,8 +634,8 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8_group(
     float amax = 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      x[2 * j] = bf16_to_f32(static_cast<uint16_t>(dw[j]));
-      x[2 * j + 1] = bf16_to_f32(static_cast<uint16_t>(dw[j] >> 16));
+      x[2 * j] = T::to_f32(static_cast<uint16_t>(dw[j]));
+      x[2 * j + 1] = T::to_f32(static_cast<uint16_t>(dw[j] >> 16));
       amax = fmaxf(amax, fmaxf(fabsf(x[2 * j]), fabsf(x[2 * j + 1])));
     }
 #pragma unroll
@@ -601,6 +662,7 @@ __global__ __launch_bounds__(256) void kvc_gather_fp8_group(
 // Sliced dequantize+scatter for group-scaled records: same shape as
 // kvc_scatter_fp8, but the scale is scales[(8 v) / G] = scales[v >> lane_shift]
 // (lane_shift = log2(G/8)) — one address per G/8-lane run, an L2-hit load.
+template <typename T>
 __global__ __launch_bounds__(256) void kvc_scatter_fp8_group(
     const void* const* __restrict__ layer_ptrs,
     const uint64_t* __restrict__ layer_strides, int num_layers,
@@ -633,8 +695,8 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp8_group(
     for (int j = 0; j < 4; ++j) {
       uint8_t b0 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16));
       uint8_t b1 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16 + 8));
-      uint16_t h0 = f32_to_bf16(fp8_e4m3_to_f32(b0) * scale);
-      uint16_t h1 = f32_to_bf16(fp8_e4m3_to_f32(b1) * scale);
+      uint16_t h0 = T::from_f32(fp8_e4m3_to_f32(b0) * scale);
+      uint16_t h1 = T::from_f32(fp8_e4m3_to_f32(b1) * scale);
       od[j] = static_cast<uint32_t>(h0) | (static_cast<uint32_t>(h1) << 16);
     }
     vout[v] = o;
@@ -666,7 +728,7 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, int group_size,
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
-    uint8_t* dst, hipStream_t stream, uint32_t footer_bytes) {
+    uint8_t* dst, hipStream_t stream, uint32_t footer_bytes, int kv_dtype) {
   const int shift = fp8_group_lane_shift(block_bytes, group_size);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
@@ -676,16 +738,18 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
-#define KVC_GATHER_GROUP(LANES)                                               \
-  hipLaunchKernelGGL(kvc_gather_fp8_group<LANES>, grid, dim3(256), 0, stream, \
-                     layer_ptrs_dev, layer_strides_dev, num_layers,           \
-                     block_bytes, bl, ids_dev, dst, footer_bytes)
-  switch (shift) {
-    case 3: KVC_GATHER_GROUP(8); break;
-    case 4: KVC_GATHER_GROUP(16); break;
-    case 5: KVC_GATHER_GROUP(32); break;
-    default: KVC_GATHER_GROUP(64); break;
-  }
+#define KVC_GATHER_GROUP(LANES)                                             \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(kvc_gather_fp8_group<LANES, T>), grid, \
+                     dim3(256), 0, stream, layer_ptrs_dev,                  \
+                     layer_strides_dev, num_layers, block_bytes, bl,        \
+                     ids_dev, dst, footer_bytes)
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype, switch (shift) {
+        case 3: KVC_GATHER_GROUP(8); break;
+        case 4: KVC_GATHER_GROUP(16); break;
+        case 5: KVC_GATHER_GROUP(32); break;
+        default: KVC_GATHER_GROUP(64); break;
+      });
 #undef KVC_GATHER_GROUP
   return hipGetLastError();
 }
@@ -694,7 +758,8 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
     int num_layers, uint64_t block_bytes, int group_size,
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
-    const uint8_t* src, hipStream_t stream, uint32_t footer_bytes) {
+    const uint8_t* src, hipStream_t stream, uint32_t footer_bytes,
+    int kv_dtype) {
   const int shift = fp8_group_lane_shift(block_bytes, group_size);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
@@ -704,9 +769,11 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
-  hipLaunchKernelGGL(kvc_scatter_fp8_group, grid, dim3(256), 0, stream,
-                     layer_ptrs_dev, layer_strides_dev, num_layers, block_bytes,
-                     shift, bl, ids_dev, src, footer_bytes);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_scatter_fp8_group<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, shift, bl, ids_dev, src, footer_bytes));
   return hipGetLastError();
 }
 

@@ -21,7 +21,8 @@ class OffloadEngineConfig:
     read_preferring_ratio: float = 0.75
     max_write_queued_seconds: float = 30.0
     copy_path: str = "staged"  # staged | zero_copy | host
-    # raw | fp8_e4m3 (bf16 pages -> fp8 + one scale per (block, layer) tile)
+    # raw | fp8_e4m3 (16-bit float pages -> fp8 + one scale per (block,
+    # layer) tile)
     # | fp8_e4m3_group (fp8 + one scale per fp8_group_size elements)
     serialize: str = "raw"
     # elements per scale for fp8_e4m3_group (set it to head_dim); one of
@@ -37,6 +38,10 @@ class OffloadEngineConfig:
     checksum: bool = False
     device: int = 0
     staging_budget_bytes: int = DEFAULT_STAGING_BUDGET_BYTES
+    # page format the fp8 modes convert from/to: auto | bfloat16 | float16.
+    # auto = float16 if every KV tensor is torch.float16, else bfloat16; an
+    # explicit value covers opaque uint8 views. Ignored by serialize="raw".
+    kv_dtype: str = "auto"
 
 
 SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group")
@@ -45,6 +50,44 @@ CHECKSUM_FOOTER_BYTES = 16
 CHECKSUM_MAGIC = 0x5343564B  # the bytes "KVCS"
 # suffix of the FileMapper dtype tag that keeps checksummed files apart
 CHECKSUM_DTYPE_SUFFIX = "+ck"
+KV_DTYPES = ("bfloat16", "float16")
+
+
+def resolve_kv_dtype(groups: Sequence[Sequence], kv_dtype: str = "auto",
+                     fp8: bool = True) -> str:
+    """Page format the fp8 codec converts with: "bfloat16" or "float16".
+
+    ``auto`` is float16 if every KV tensor is ``torch.float16`` and bfloat16
+    otherwise (bf16 tensors, and the opaque uint8 views of bf16 bits that
+    predate this option). An explicit value covers uint8 views of fp16
+    pages. Raises ValueError for a value outside auto|bfloat16|float16, and,
+    when ``fp8`` is true, for an engine that mixes float16 and bfloat16
+    tensors or an explicit value that contradicts a tensor's own 16-bit
+    float dtype (either direction). ``fp8=False`` (serialize="raw") never
+    converts, so nothing is checked beyond the spelling."""
+    import torch
+
+    if kv_dtype not in ("auto",) + KV_DTYPES:
+        raise ValueError(
+            f"kv_dtype must be one of auto|{'|'.join(KV_DTYPES)}, "
+            f"got {kv_dtype!r}")
+    names = {torch.float16: "float16", torch.bfloat16: "bfloat16"}
+    tensors = [t for g in groups for t in g]
+    seen = {names[t.dtype] for t in tensors if t.dtype in names}
+    if fp8:
+        if len(seen) > 1:
+            raise ValueError(
+                "KV tensors mix float16 and bfloat16; the fp8 codec needs one "
+                "page format per engine")
+        if kv_dtype != "auto" and seen and kv_dtype not in seen:
+            raise ValueError(
+                f"kv_dtype={kv_dtype!r} contradicts KV tensors of dtype "
+                f"torch.{next(iter(seen))}")
+    if kv_dtype != "auto":
+        return kv_dtype
+    if tensors and all(t.dtype == torch.float16 for t in tensors):
+        return "float16"
+    return "bfloat16"
 
 
 def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
@@ -121,6 +164,10 @@ class TorchOffloadEngine:
                 "use copy_path='host' for CPU tensors"
             )
 
+        # resolved page format of the fp8 modes ("bfloat16" | "float16")
+        self.kv_dtype = resolve_kv_dtype(
+            groups, config.kv_dtype, fp8=config.serialize != "raw")
+
         native_groups = []
         self.group_geometry: List[dict] = []
         max_file_bytes = 0
@@ -193,6 +240,7 @@ class TorchOffloadEngine:
             direct_io=config.direct_io,
             fp8_group_size=config.fp8_group_size,
             checksum=config.checksum,
+            kv_dtype=self.kv_dtype,
         )
         del stream
         # keep tensor refs: the native engine holds raw pointers

@@ -38,6 +38,9 @@ class ObjStorageConfig:
     secret_key: str = ""
     session_token: str = ""
     region: str = "us-east-1"
+    # page format of the fp8 modes: auto | bfloat16 | float16, resolved like
+    # OffloadEngineConfig.kv_dtype (offload.engine.resolve_kv_dtype)
+    kv_dtype: str = "auto"
 
 
 _EMPTY_SHA256 = hashlib.sha256(b"").hexdigest()
@@ -159,12 +162,14 @@ class ObjStorageEngine:
         import torch
 
         from .. import ensure_offload_native
-        from .engine import tile_record_bytes
+        from .engine import resolve_kv_dtype, tile_record_bytes
 
         ko = ensure_offload_native()
         self._torch = torch
         self.config = config
         self.gpu_mode = groups[0][0].is_cuda
+        self.kv_dtype = resolve_kv_dtype(
+            groups, config.kv_dtype, fp8=config.serialize != "raw")
         native_groups = []
         self.group_geometry: List[dict] = []
         self._fp8_group = config.serialize == "fp8_e4m3_group"
@@ -185,7 +190,8 @@ class ObjStorageEngine:
             )
         self._fp8 = config.serialize == "fp8_e4m3"
         device = groups[0][0].device.index or 0 if self.gpu_mode else 0
-        self._copier = ko.BlockCopier(native_groups, self.gpu_mode, device)
+        self._copier = ko.BlockCopier(native_groups, self.gpu_mode, device,
+                                      kv_dtype=self.kv_dtype)
         self._tensors = [list(g) for g in groups]
         self.client = ObjClient(config)
         self._pool = concurrent.futures.ThreadPoolExecutor(

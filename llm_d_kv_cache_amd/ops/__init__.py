@@ -14,6 +14,11 @@ built from, for embedding in other MI355X services.
   (64/128/256/512; set it to head_dim) instead of one per tile. The gather
   is a single pass — the group amax is an in-wave butterfly — and needs no
   scratch. serialize="fp8_e4m3_group" rides these kernels.
+- page format: both fp8 families convert bf16 or fp16 pages. The copier is
+  built for one format (block_copier(..., kv_dtype="auto"): float16 if
+  every page tensor is torch.float16, else bfloat16; pass "float16" /
+  "bfloat16" for opaque uint8 views) and every fp8 method follows it. The
+  records are format-free, so the two ends of a transfer need not agree.
 - record checksums: packed_bytes*/gather*/scatter* take checksum=True to
   leave a 16-byte footer behind every record; seal_records(ptr, tiles,
   payload_bytes, stream) fills the footers of such a slab and
@@ -25,9 +30,14 @@ from __future__ import annotations
 from typing import List, Optional, Sequence
 
 
-def block_copier(groups: Sequence[Sequence], device: Optional[int] = None):
-    """BlockCopier over torch page tensors (GPU or CPU twins)."""
+def block_copier(groups: Sequence[Sequence], device: Optional[int] = None,
+                 kv_dtype: str = "auto"):
+    """BlockCopier over torch page tensors (GPU or CPU twins).
+
+    kv_dtype (auto | bfloat16 | float16) is the page format every fp8 method
+    of the copier converts with; see offload.engine.resolve_kv_dtype."""
     from .. import ensure_offload_native
+    from ..offload.engine import resolve_kv_dtype
 
     ko = ensure_offload_native()
     gpu = groups[0][0].is_cuda
@@ -40,7 +50,8 @@ def block_copier(groups: Sequence[Sequence], device: Optional[int] = None):
     ]
     dev = device if device is not None else (
         groups[0][0].device.index or 0 if gpu else 0)
-    return ko.BlockCopier(native, gpu, dev)
+    return ko.BlockCopier(native, gpu, dev,
+                          kv_dtype=resolve_kv_dtype(groups, kv_dtype))
 
 
 def record_checksum(buffer) -> int:

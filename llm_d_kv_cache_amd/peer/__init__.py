@@ -85,20 +85,26 @@ class _OpTracker:
 class PeerMigrationService:
     def __init__(self, groups: Sequence[Sequence], data_group=None,
                  control_group=None, device: Optional[int] = None,
-                 poll_interval_s: float = 0.0002, dram_lookup=None):
+                 poll_interval_s: float = 0.0002, dram_lookup=None,
+                 kv_dtype: str = "auto"):
         """groups: per KV-cache group, a list of per-layer page tensors
         (the offload engine's layout). data_group: nccl(=RCCL) on GPU /
         gloo on CPU. control_group: gloo. Both must be dedicated groups.
         dram_lookup: optional (chunk_hash, group, n_blocks) ->
         (host_uint8_tensor, is_fp8) | None — lets this rank serve pulls
         from its pinned host-DRAM cache after HBM eviction (see
-        peer.tiered.make_dram_lookup)."""
+        peer.tiered.make_dram_lookup).
+        kv_dtype: page format of the fp8 pulls, auto | bfloat16 | float16,
+        resolved like OffloadEngineConfig.kv_dtype. fp8 records are
+        format-free, so both ends simply convert with their own value."""
         import torch
         import torch.distributed as dist
 
         from .. import ensure_offload_native
+        from ..offload.engine import resolve_kv_dtype
 
         _kvoffload = ensure_offload_native()
+        self.kv_dtype = resolve_kv_dtype(groups, kv_dtype)
 
         self._torch = torch
         self._dist = dist
@@ -121,7 +127,8 @@ class PeerMigrationService:
             native_groups.append((ptrs, strides, strides[0], int(g[0].shape[0])))
             self._geo.append({"num_layers": len(g), "block_bytes": strides[0]})
         self._copier = _kvoffload.BlockCopier(native_groups, self.gpu_mode,
-                                              self.device)
+                                              self.device,
+                                              kv_dtype=self.kv_dtype)
         self._tensors = [list(g) for g in groups]
 
         self._registry: Dict[Tuple[int, int], List[int]] = {}
