@@ -59,7 +59,7 @@ PYBIND11_MODULE(_kvoffload, m) {
                        const std::string& serialize, size_t host_cache_bytes,
                        const std::string& write_policy, bool direct_io,
                        int fp8_group_size, bool checksum,
-                       const std::string& kv_dtype) {
+                       const std::string& kv_dtype, int fp4_group_size) {
              EngineConfig cfg;
              cfg.kv_dtype = parse_kv_dtype(kv_dtype);
              cfg.checksum = checksum;
@@ -84,10 +84,14 @@ PYBIND11_MODULE(_kvoffload, m) {
                cfg.serialize = Serialize::kFp8E4M3;
              else if (serialize == "fp8_e4m3_group")
                cfg.serialize = Serialize::kFp8E4M3Group;
+             else if (serialize == "fp4_e2m1_group")
+               cfg.serialize = Serialize::kFp4E2M1Group;
              else
                throw std::invalid_argument(
-                   "serialize must be raw|fp8_e4m3|fp8_e4m3_group");
+                   "serialize must be "
+                   "raw|fp8_e4m3|fp8_e4m3_group|fp4_e2m1_group");
              cfg.fp8_group_size = fp8_group_size;
+             cfg.fp4_group_size = fp4_group_size;
              cfg.host_cache_bytes = host_cache_bytes;
              if (write_policy == "through")
                cfg.write_policy = WritePolicy::kThrough;
@@ -116,7 +120,7 @@ PYBIND11_MODULE(_kvoffload, m) {
            py::arg("serialize") = "raw", py::arg("host_cache_bytes") = 0,
            py::arg("write_policy") = "through", py::arg("direct_io") = false,
            py::arg("fp8_group_size") = 128, py::arg("checksum") = false,
-           py::arg("kv_dtype") = "bfloat16")
+           py::arg("kv_dtype") = "bfloat16", py::arg("fp4_group_size") = 32)
       .def(
           "async_store",
           [](StorageOffloadEngine& e,
@@ -277,6 +281,31 @@ PYBIND11_MODULE(_kvoffload, m) {
           },
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
           py::arg("group_size") = 128, py::arg("stream") = 0,
+          py::arg("checksum") = false)
+      .def("packed_bytes_fp4_group", &BlockCopier::packed_bytes_fp4_group,
+           py::arg("group"), py::arg("n_blocks"), py::arg("group_size") = 32,
+           py::arg("checksum") = false)
+      .def(
+          "gather_fp4_group",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
+             int group_size, uintptr_t stream, bool checksum) {
+            py::gil_scoped_release rel;
+            c.gather_fp4_group(group, ids, reinterpret_cast<void*>(dst),
+                               group_size, stream, checksum);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("dst"),
+          py::arg("group_size") = 32, py::arg("stream") = 0,
+          py::arg("checksum") = false)
+      .def(
+          "scatter_fp4_group",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
+             int group_size, uintptr_t stream, bool checksum) {
+            py::gil_scoped_release rel;
+            c.scatter_fp4_group(group, ids, reinterpret_cast<const void*>(src),
+                                group_size, stream, checksum);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("src"),
+          py::arg("group_size") = 32, py::arg("stream") = 0,
           py::arg("checksum") = false)
       .def(
           "gather",

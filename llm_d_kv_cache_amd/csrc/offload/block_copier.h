@@ -10,7 +10,8 @@
 // verify_records() checks them.
 //
 // kv_dtype (bf16 by default) is the format of the 16-bit pages; every fp8
-// method of the copier converts with it, the raw ones never look at it.
+// and fp4 method of the copier converts with it, the raw ones never look at
+// it.
 #pragma once
 
 #include <mutex>
@@ -221,6 +222,65 @@ class BlockCopier {
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
+  // Group-scaled fp4 (e2m1) record size: block_bytes/4 code bytes + one f32
+  // scale per group_size elements, per tile.
+  size_t packed_bytes_fp4_group(int group, size_t n_blocks, int group_size,
+                                bool checksum = false) const {
+    const GroupDesc& g = groups_.at(group);
+    check_fp4_group_size(g, group_size);
+    return n_blocks * g.layer_ptrs.size() *
+           (StorageOffloadEngine::fp4_group_record_bytes(g.block_bytes,
+                                                         group_size) +
+            footer(checksum));
+  }
+
+  // Single-pass gather + per-group fp4 quantize into dst (device ptr in GPU
+  // mode); needs no scratch. Host mode uses the software twin.
+  void gather_fp4_group(int group, const std::vector<int32_t>& ids, void* dst,
+                        int group_size, uintptr_t stream,
+                        bool checksum = false) {
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_fp4_group_size(g, group_size);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp4_group_copy(
+          g, ids, static_cast<uint8_t*>(dst), group_size, /*quantize=*/true,
+          footer(checksum), kv_dtype_);
+      return;
+    }
+    hipError_t err = kvc_launch_gather_fp4_group(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
+        nullptr, static_cast<uint8_t*>(dst),
+        reinterpret_cast<hipStream_t>(stream), footer(checksum),
+        static_cast<int>(kv_dtype_));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
+  // Dequantize + scatter from a group-scaled fp4 record slab.
+  void scatter_fp4_group(int group, const std::vector<int32_t>& ids,
+                         const void* src, int group_size, uintptr_t stream,
+                         bool checksum = false) {
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_fp4_group_size(g, group_size);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp4_group_copy(
+          g, ids, const_cast<uint8_t*>(static_cast<const uint8_t*>(src)),
+          group_size, /*quantize=*/false, footer(checksum), kv_dtype_);
+      return;
+    }
+    hipError_t err = kvc_launch_scatter_fp4_group(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, group_size, ids.data(), static_cast<int>(ids.size()),
+        nullptr, static_cast<const uint8_t*>(src),
+        reinterpret_cast<hipStream_t>(stream), footer(checksum),
+        static_cast<int>(kv_dtype_));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
   // Gather block_ids of `group` into contiguous dst (device ptr in GPU
   // mode). Async on `stream`; caller synchronizes.
   void gather(int group, const std::vector<int32_t>& ids, void* dst,
@@ -312,6 +372,18 @@ class BlockCopier {
       throw std::invalid_argument(
           "block_bytes/2 = " + std::to_string(g.block_bytes / 2) +
           " elements is not a multiple of fp8 group_size " +
+          std::to_string(group_size));
+  }
+
+  static void check_fp4_group_size(const GroupDesc& g, int group_size) {
+    if (!fp4_group_size_ok(group_size))
+      throw std::invalid_argument(
+          "fp4 group_size must be 16, 32, 64 or 128 (got " +
+          std::to_string(group_size) + ")");
+    if (g.block_bytes % 16 != 0 || (g.block_bytes / 2) % group_size != 0)
+      throw std::invalid_argument(
+          "block_bytes/2 = " + std::to_string(g.block_bytes / 2) +
+          " elements is not a multiple of fp4 group_size " +
           std::to_string(group_size));
   }
 

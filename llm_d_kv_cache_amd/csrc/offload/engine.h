@@ -67,6 +67,13 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
 extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
     int, const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
+// group-scaled fp4 (e2m1): same argument lists as the fp8-group pair
+extern "C" hipError_t kvc_launch_gather_fp4_group(
+    const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
+    int, const int32_t*, uint8_t*, hipStream_t, uint32_t, int);
+extern "C" hipError_t kvc_launch_scatter_fp4_group(
+    const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
+    int, const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
 // Record checksums (checksum.h has the format and the host twin). slab holds
 // `tiles` records of payload_bytes + 16; scratch is
 // kvc_checksum_scratch_bytes(tiles) of 8-byte aligned device memory; result
@@ -101,11 +108,14 @@ enum class CopyPath { kStaged, kZeroCopy, kHostMemcpy };
 // float pages (halves wire + storage bytes; one f32 scale per (block, layer)
 // tile appended to each tile record). kFp8E4M3Group scales every
 // fp8_group_size-element run on its own (users set it to head_dim): the
-// record is [ n fp8 | n/G f32 scales ], n = block_bytes/2.
-enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group };
+// record is [ n fp8 | n/G f32 scales ], n = block_bytes/2. kFp4E2M1Group is
+// the same design one step narrower: OCP e2m1 codes, two per byte, one f32
+// scale per fp4_group_size elements; the record is
+// [ n/2 code bytes | n/G f32 scales ].
+enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group, kFp4E2M1Group };
 
-// Format of the 16-bit KV pages the fp8 modes read on store and write on
-// load (raw copies never look at it). The records are format-free; only the
+// Format of the 16-bit KV pages the fp8 and fp4 modes read on store and
+// write on load (raw copies never look at it). The records are format-free; only the
 // page <-> f32 conversions differ. The values are the kv_dtype argument of
 // the fp8 launchers in kernels.hip.
 enum class KvDtype : int { kBf16 = 0, kFp16 = 1 };
@@ -119,6 +129,10 @@ inline KvDtype parse_kv_dtype(const std::string& s) {
 
 inline bool fp8_group_size_ok(int g) {
   return g == 64 || g == 128 || g == 256 || g == 512;
+}
+
+inline bool fp4_group_size_ok(int g) {
+  return g == 16 || g == 32 || g == 64 || g == 128;
 }
 
 // Store completion semantics: kThrough = the file rename happened (crash
@@ -146,6 +160,7 @@ struct EngineConfig {
   CopyPath copy_path = CopyPath::kStaged;
   Serialize serialize = Serialize::kRaw;
   int fp8_group_size = 128;  // elements per scale; kFp8E4M3Group only
+  int fp4_group_size = 32;   // elements per scale; kFp4E2M1Group only
   // Pinned host-DRAM cache tier (0 = disabled): write-through on store,
   // cache-hit loads skip the filesystem (host_cache.h).
   size_t host_cache_bytes = 0;
@@ -159,7 +174,7 @@ struct EngineConfig {
   // page is written. Files with and without footers must not share a
   // directory: tag the FileMapper dtype with "+ck" (docs/configuration.md).
   bool checksum = false;
-  // Page format of the KV tensors; consulted only by the fp8 modes.
+  // Page format of the KV tensors; consulted only by the fp8 and fp4 modes.
   KvDtype kv_dtype = KvDtype::kBf16;
 };
 
@@ -235,6 +250,11 @@ class StorageOffloadEngine {
       throw std::invalid_argument(
           "fp8_group_size must be 64, 128, 256 or 512 (got " +
           std::to_string(cfg_.fp8_group_size) + ")");
+    const bool fp4 = cfg_.serialize == Serialize::kFp4E2M1Group;
+    if (fp4 && !fp4_group_size_ok(cfg_.fp4_group_size))
+      throw std::invalid_argument(
+          "fp4_group_size must be 16, 32, 64 or 128 (got " +
+          std::to_string(cfg_.fp4_group_size) + ")");
     // Staging is sized from raw block_bytes (the fp8 layouts are smaller and
     // the split fp8 gather keeps its scratch in the difference). With
     // footers raw is block_bytes + 16 per tile and nothing is left over, so
@@ -252,6 +272,12 @@ class StorageOffloadEngine {
             std::to_string(g.block_bytes / 2) +
             " elements is not a multiple of fp8_group_size " +
             std::to_string(cfg_.fp8_group_size));
+      if (fp4 && (g.block_bytes / 2) % cfg_.fp4_group_size != 0)
+        throw std::invalid_argument(
+            "group " + std::to_string(gi) + ": block_bytes/2 = " +
+            std::to_string(g.block_bytes / 2) +
+            " elements is not a multiple of fp4_group_size " +
+            std::to_string(cfg_.fp4_group_size));
       if (g.layer_ptrs.size() != g.layer_strides.size())
         throw std::invalid_argument("layer ptr/stride length mismatch");
       if (cfg_.checksum) {
@@ -610,6 +636,8 @@ class StorageOffloadEngine {
         return g.block_bytes / 2 + 4;
       case Serialize::kFp8E4M3Group:
         return fp8_group_record_bytes(g.block_bytes, cfg_.fp8_group_size);
+      case Serialize::kFp4E2M1Group:
+        return fp4_group_record_bytes(g.block_bytes, cfg_.fp4_group_size);
       default:
         return g.block_bytes;
     }
@@ -776,6 +804,13 @@ class StorageOffloadEngine {
             const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
             dev_layer_strides_[ft.group], nl, g.block_bytes,
             cfg_.fp8_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
+            ctx.stream, footer_bytes(), static_cast<int>(cfg_.kv_dtype));
+      } else if (cfg_.serialize == Serialize::kFp4E2M1Group) {
+        // the same single-pass shape, for both destinations
+        err = kvc_launch_gather_fp4_group(
+            const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
+            dev_layer_strides_[ft.group], nl, g.block_bytes,
+            cfg_.fp4_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
             ctx.stream, footer_bytes(), static_cast<int>(cfg_.kv_dtype));
       } else if (cfg_.serialize == Serialize::kFp8E4M3) {
         if (cfg_.copy_path == CopyPath::kStaged) {
@@ -994,7 +1029,7 @@ class StorageOffloadEngine {
     return false;
   }
 
-  // Scatter (raw), or dequantize+scatter (either fp8 mode), of the packed
+  // Scatter (raw), or dequantize+scatter (fp8 and fp4 modes), of the packed
   // records at `src` into the pages of ft.block_ids.
   hipError_t launch_scatter(WorkerCtx& ctx, const FileTransfer& ft,
                             const int32_t* ids_dev, const uint8_t* src) {
@@ -1008,6 +1043,11 @@ class StorageOffloadEngine {
       case Serialize::kFp8E4M3Group:
         return kvc_launch_scatter_fp8_group(
             ptrs, strides, nl, g.block_bytes, cfg_.fp8_group_size,
+            ft.block_ids.data(), nb, ids_dev, src, ctx.stream,
+            footer_bytes(), static_cast<int>(cfg_.kv_dtype));
+      case Serialize::kFp4E2M1Group:
+        return kvc_launch_scatter_fp4_group(
+            ptrs, strides, nl, g.block_bytes, cfg_.fp4_group_size,
             ft.block_ids.data(), nb, ids_dev, src, ctx.stream,
             footer_bytes(), static_cast<int>(cfg_.kv_dtype));
       case Serialize::kFp8E4M3:
@@ -1206,6 +1246,9 @@ class StorageOffloadEngine {
         else if (cfg_.serialize == Serialize::kFp8E4M3Group)
           fp8_group_quantize_tile(src, g.block_bytes, cfg_.fp8_group_size, out,
                                   cfg_.kv_dtype);
+        else if (cfg_.serialize == Serialize::kFp4E2M1Group)
+          fp4_group_quantize_tile(src, g.block_bytes, cfg_.fp4_group_size, out,
+                                  cfg_.kv_dtype);
         else
           std::memcpy(out, src, g.block_bytes);
       }
@@ -1225,6 +1268,9 @@ class StorageOffloadEngine {
           fp8_dequantize_tile(in, g.block_bytes, dst, cfg_.kv_dtype);
         else if (cfg_.serialize == Serialize::kFp8E4M3Group)
           fp8_group_dequantize_tile(in, g.block_bytes, cfg_.fp8_group_size, dst,
+                                    cfg_.kv_dtype);
+        else if (cfg_.serialize == Serialize::kFp4E2M1Group)
+          fp4_group_dequantize_tile(in, g.block_bytes, cfg_.fp4_group_size, dst,
                                     cfg_.kv_dtype);
         else
           std::memcpy(dst, in, g.block_bytes);
@@ -1339,6 +1385,28 @@ class StorageOffloadEngine {
     return sign ? -v : v;
   }
 
+  // ---- software fp4 e2m1 (host twin of the fp4-group kernels) --------------
+  // Round-to-nearest-even onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating, as
+  // the compare chain that defines the format (the kernels use the gfx950
+  // packed convert, which returns the same code for every finite f32). A
+  // tie goes to the even code, so the thresholds alternate between > and
+  // >=; the sign bit is copied whatever the magnitude rounds to. Finite
+  // inputs only.
+  static uint8_t f32_to_fp4_rne(float t) {
+    uint32_t w;
+    std::memcpy(&w, &t, 4);
+    const float a = std::abs(t);
+    const uint32_t mag = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) +
+                         (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.0f);
+    return static_cast<uint8_t>(((w >> 28) & 8u) | mag);
+  }
+  static float fp4_to_f32(uint8_t code) {
+    static constexpr float kMag[8] = {0.0f, 0.5f, 1.0f, 1.5f,
+                                      2.0f, 3.0f, 4.0f, 6.0f};
+    const float m = kMag[code & 7];
+    return (code & 8) ? -m : m;
+  }
+
   public:
   // Shared software fp8 path (BlockCopier's host mode reuses it).
   // footer: bytes every record carries behind its payload (0 or 16).
@@ -1390,6 +1458,36 @@ class StorageOffloadEngine {
     }
   }
 
+  static size_t fp4_group_record_bytes(uint64_t block_bytes, int group_size) {
+    const size_t n = block_bytes / 2;
+    return n / 2 + 4 * (n / static_cast<size_t>(group_size));
+  }
+
+  // Software twin of kvc_gather_fp4_group / kvc_scatter_fp4_group (engine
+  // host mode and BlockCopier's CPU path): same bytes as the kernels.
+  static void host_fp4_group_copy(const GroupDesc& g,
+                                  const std::vector<int32_t>& ids,
+                                  uint8_t* packed, int group_size,
+                                  bool quantize, size_t footer = 0,
+                                  KvDtype kv_dtype = KvDtype::kBf16) {
+    const size_t nl = g.layer_ptrs.size();
+    const size_t rec =
+        fp4_group_record_bytes(g.block_bytes, group_size) + footer;
+    for (size_t bi = 0; bi < ids.size(); ++bi) {
+      for (size_t l = 0; l < nl; ++l) {
+        uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +
+                        static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
+        uint8_t* slab = packed + (bi * nl + l) * rec;
+        if (quantize)
+          fp4_group_quantize_tile(page, g.block_bytes, group_size, slab,
+                                  kv_dtype);
+        else
+          fp4_group_dequantize_tile(slab, g.block_bytes, group_size, page,
+                                    kv_dtype);
+      }
+    }
+  }
+
   private:
   // Record starts are only 4-byte aligned and scales follow n payload
   // bytes: scales move through memcpy.
@@ -1424,6 +1522,52 @@ class StorageOffloadEngine {
       std::memcpy(&scale, in + n + 4 * gi, 4);
       for (size_t i = 0; i < G; ++i)
         out[gi * G + i] = T::from_f32(fp8_to_f32(in[gi * G + i]) * scale);
+    }
+  }
+
+  // fp4: G is even, so a group starts on a byte boundary. The product
+  // f32(value) * scale is rounded to f32 first and T::from_f32 then rounds
+  // those bits to the page type in integer arithmetic: the two roundings of
+  // the spec, for fp16 as for bf16 (one rounding differs for fp16
+  // subnormal results; see fp4_page_from_product in kernels.hip).
+  template <typename T>
+  static void fp4_group_quantize_tile_t(const uint8_t* src, size_t block_bytes,
+                                        int group_size, uint8_t* out) {
+    const size_t n = block_bytes / 2;
+    const size_t G = static_cast<size_t>(group_size);
+    const uint16_t* in = reinterpret_cast<const uint16_t*>(src);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      const uint16_t* x = in + gi * G;
+      float amax = 0.0f;
+      for (size_t i = 0; i < G; ++i)
+        amax = std::max(amax, std::abs(T::to_f32(x[i])));
+      if (amax <= 0.0f) amax = 1.0f;
+      const float scale = amax / 6.0f;
+      const float inv = 6.0f / amax;
+      uint8_t* codes = out + gi * G / 2;
+      for (size_t i = 0; i < G; i += 2)
+        codes[i / 2] = static_cast<uint8_t>(
+            f32_to_fp4_rne(T::to_f32(x[i]) * inv) |
+            (f32_to_fp4_rne(T::to_f32(x[i + 1]) * inv) << 4));
+      std::memcpy(out + n / 2 + 4 * gi, &scale, 4);
+    }
+  }
+
+  template <typename T>
+  static void fp4_group_dequantize_tile_t(const uint8_t* in, size_t block_bytes,
+                                          int group_size, uint8_t* dst) {
+    const size_t n = block_bytes / 2;
+    const size_t G = static_cast<size_t>(group_size);
+    uint16_t* out = reinterpret_cast<uint16_t*>(dst);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      float scale;
+      std::memcpy(&scale, in + n / 2 + 4 * gi, 4);
+      const uint8_t* codes = in + gi * G / 2;
+      for (size_t i = 0; i < G; i += 2) {
+        out[gi * G + i] = T::from_f32(fp4_to_f32(codes[i / 2] & 0xf) * scale);
+        out[gi * G + i + 1] =
+            T::from_f32(fp4_to_f32(codes[i / 2] >> 4) * scale);
+      }
     }
   }
 
@@ -1474,6 +1618,22 @@ class StorageOffloadEngine {
       fp8_group_dequantize_tile_t<PageFp16>(in, block_bytes, group_size, dst);
     else
       fp8_group_dequantize_tile_t<PageBf16>(in, block_bytes, group_size, dst);
+  }
+  static void fp4_group_quantize_tile(const uint8_t* src, size_t block_bytes,
+                                      int group_size, uint8_t* out,
+                                      KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp4_group_quantize_tile_t<PageFp16>(src, block_bytes, group_size, out);
+    else
+      fp4_group_quantize_tile_t<PageBf16>(src, block_bytes, group_size, out);
+  }
+  static void fp4_group_dequantize_tile(const uint8_t* in, size_t block_bytes,
+                                        int group_size, uint8_t* dst,
+                                        KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp4_group_dequantize_tile_t<PageFp16>(in, block_bytes, group_size, dst);
+    else
+      fp4_group_dequantize_tile_t<PageBf16>(in, block_bytes, group_size, dst);
   }
   static void fp8_quantize_tile(const uint8_t* src, size_t block_bytes,
                                 uint8_t* out, KvDtype kv_dtype) {

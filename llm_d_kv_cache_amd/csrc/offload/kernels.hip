@@ -777,6 +777,254 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
   return hipGetLastError();
 }
 
+// ---- group-scaled fp4 (OCP e2m1, one f32 scale per G-element run) ------------
+// serialize="fp4_e2m1_group": a tile record is
+//   [ n/2 code bytes | n/G f32 scales ],  n = block_bytes/2,  n % G == 0
+// with G in {16, 32, 64, 128}; element 2i sits in bits 3:0 of byte i, element
+// 2i+1 in bits 7:4. The kernels keep the shape of the fp8-group pair: at 8
+// page values per lane a group is G/8 = 2..16 consecutive lanes of one wave,
+// a lane loads 16 B and stores ONE dword of codes, the group's first lane
+// stores the scale.
+//
+// Per group, all f32: amax = max|x| (0 -> 1), scale = amax/6 (stored),
+// t = x * (6/amax), code = sign(x) << 3 | mag(|t|) with mag round-to-nearest-
+// even on the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating; load:
+// y = T_RNE(f32(value(code)) * scale), T the page type.
+
+namespace {
+
+constexpr float kFp4Max = 6.0f;  // e2m1 max normal
+
+typedef float kvc_float2 __attribute__((ext_vector_type(2)));
+
+// Eight scaled values -> one dword of codes, element j in bits 4j+3:4j, with
+// the gfx950 packed convert (v_cvt_scalef32_pk_fp4_f32 at scale 1.0: two
+// values per instruction, into the selected byte). The format is defined by
+// the compare chain of the host twin (engine.h f32_to_fp4_rne: RNE, ties to
+// the even code, saturating at 6, the sign bit always copied, so -0.0 and
+// negatives that round to zero give 0x8); the instruction returned the
+// chain's code for every finite f32 bit pattern when the two were compared
+// exhaustively on an MI355X, and the tests hold both to the oracle's bytes.
+// A compare chain here costs ~17 VALU instructions per value and made the
+// gather compute-bound (profiles/fp4_group_kernels.md).
+__device__ __forceinline__ uint32_t fp4_e2m1_pack8(const float (&t)[8]) {
+  uint32_t out = 0;
+  // byte_sel must be an immediate: unrolled by hand
+  out = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(out, t[0], t[1], 1.0f, 0);
+  out = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(out, t[2], t[3], 1.0f, 1);
+  out = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(out, t[4], t[5], 1.0f, 2);
+  out = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(out, t[6], t[7], 1.0f, 3);
+  return out;
+}
+
+// Byte kByte of a code dword -> its two values (low nibble first); exact, no
+// rounding is involved (v_cvt_scalef32_pk_f32_fp4 at scale 1.0).
+template <int kByte>
+__device__ __forceinline__ kvc_float2 fp4_e2m1_unpack2(uint32_t codes) {
+  return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes, 1.0f, kByte);
+}
+
+// Page value of an f32 product that has ALREADY been rounded to f32: the
+// second of the spec's two roundings. Unlike the fp8 records (see
+// PageFp16::from_f32), fp4 records do hit fp16 ties where one rounding of
+// the exact product and two roundings differ (magnitudes 1.5 and 3.0 times
+// a scale amax/6, subnormal results), so the fp16 form must not let the
+// compiler fold product and cast into one mixed-precision FMA: the empty
+// asm makes the f32 product opaque, and the cast that follows is a plain
+// v_cvt_f16_f32 (RNE, fp16 subnormals kept). bf16 rounds in integer
+// arithmetic on the f32 bits and cannot be folded.
+template <typename T>
+__device__ __forceinline__ uint16_t fp4_page_from_product(float p) {
+  return T::from_f32(p);
+}
+template <>
+__device__ __forceinline__ uint16_t fp4_page_from_product<PageFp16>(float p) {
+  asm("" : "+v"(p));
+  return __builtin_bit_cast(uint16_t, static_cast<_Float16>(p));
+}
+
+}  // namespace
+
+// kLanes = G/8 lanes per group. Same loop as kvc_gather_fp8_group: a
+// WAVE-UNIFORM grid-stride base with a guarded body, so every lane reaches
+// every shuffle; groups are kLanes-aligned runs of v and n % G == 0, so a
+// group is wholly inside the tile or wholly past its end, and the xor
+// butterfly (offsets < kLanes) never leaves it.
+template <int kLanes, typename T>
+__global__ __launch_bounds__(256) void kvc_gather_fp4_group(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
+  static_assert(kLanes == 2 || kLanes == 4 || kLanes == 8 || kLanes == 16,
+                "group must span 2..16 lanes of one wave");
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes / 2;
+  const uint64_t n_groups = n_elems / (8 * kLanes);
+  const uint64_t record = n_elems / 2 + 4 * n_groups + footer_bytes;
+  const uint4* __restrict__ vsrc = reinterpret_cast<const uint4*>(
+      static_cast<const uint8_t*>(layer_ptrs[l]) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  uint8_t* __restrict__ payload = dst + static_cast<uint64_t>(tile) * record;
+  uint32_t* __restrict__ vout = reinterpret_cast<uint32_t*>(payload);
+  float* __restrict__ scales = reinterpret_cast<float*>(payload + n_elems / 2);
+  const uint64_t nvec = n_elems / 8;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t vb = static_cast<uint64_t>(blockIdx.y) * blockDim.x +
+                     (threadIdx.x & ~63u);
+       vb < nvec; vb += stride) {
+    const uint64_t v = vb + lane;
+    const bool live = v < nvec;
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (live) w = vsrc[v];
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
+    float x[8];
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[2 * j] = T::to_f32(static_cast<uint16_t>(dw[j]));
+      x[2 * j + 1] = T::to_f32(static_cast<uint16_t>(dw[j] >> 16));
+      amax = fmaxf(amax, fmaxf(fabsf(x[2 * j]), fabsf(x[2 * j + 1])));
+    }
+#pragma unroll
+    for (int off = kLanes / 2; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    if (amax <= 0.0f) amax = 1.0f;
+    const float inv_scale = kFp4Max / amax;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] *= inv_scale;
+    const uint32_t out = fp4_e2m1_pack8(x);
+    if (live) {
+      vout[v] = out;
+      if ((lane & (kLanes - 1)) == 0) scales[v / kLanes] = amax / kFp4Max;
+    }
+  }
+}
+
+// Sliced dequantize+scatter for fp4 records: the shape of
+// kvc_scatter_fp8_group. A lane reads one dword of codes and writes 8 page
+// values as one dwordx4; its scale is scales[(8 v) / G] = scales[v >>
+// lane_shift] (lane_shift = log2(G/8)), one address per G/8-lane run.
+template <typename T>
+__global__ __launch_bounds__(256) void kvc_scatter_fp4_group(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, int lane_shift, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes / 2;
+  const uint64_t nvec = n_elems / 8;
+  const uint64_t record = n_elems / 2 + 4 * (nvec >> lane_shift) + footer_bytes;
+  uint4* __restrict__ vout = reinterpret_cast<uint4*>(
+      static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  const uint8_t* __restrict__ payload =
+      src + static_cast<uint64_t>(tile) * record;
+  const uint32_t* __restrict__ vin = reinterpret_cast<const uint32_t*>(payload);
+  const float* __restrict__ scales =
+      reinterpret_cast<const float*>(payload + n_elems / 2);
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  for (uint64_t v = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
+       v < nvec; v += stride) {
+    const float scale = scales[v >> lane_shift];
+    const uint32_t codes = vin[v];
+    // byte_sel must be an immediate: unrolled by hand
+    const kvc_float2 val[4] = {
+        fp4_e2m1_unpack2<0>(codes), fp4_e2m1_unpack2<1>(codes),
+        fp4_e2m1_unpack2<2>(codes), fp4_e2m1_unpack2<3>(codes)};
+    uint4 o;
+    uint32_t* od = reinterpret_cast<uint32_t*>(&o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint16_t h0 = fp4_page_from_product<T>(val[j].x * scale);
+      uint16_t h1 = fp4_page_from_product<T>(val[j].y * scale);
+      od[j] = static_cast<uint32_t>(h0) | (static_cast<uint32_t>(h1) << 16);
+    }
+    vout[v] = o;
+  }
+}
+
+namespace {
+
+// G -> log2(G/8); -1 for anything but 16/32/64/128 or a tile the group size
+// does not divide.
+inline int fp4_group_lane_shift(uint64_t block_bytes, int group_size) {
+  int shift;
+  switch (group_size) {
+    case 16: shift = 1; break;
+    case 32: shift = 2; break;
+    case 64: shift = 3; break;
+    case 128: shift = 4; break;
+    default: return -1;
+  }
+  if (block_bytes % 16 != 0 ||
+      (block_bytes / 2) % static_cast<uint64_t>(group_size) != 0)
+    return -1;
+  return shift;
+}
+
+}  // namespace
+
+extern "C" hipError_t kvc_launch_gather_fp4_group(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, int group_size,
+    const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
+    uint8_t* dst, hipStream_t stream, uint32_t footer_bytes, int kv_dtype) {
+  const int shift = fp4_group_lane_shift(block_bytes, group_size);
+  if (shift < 0) return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = copy_grid(tiles, block_bytes);
+#define KVC_GATHER_FP4_GROUP(LANES)                                         \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(kvc_gather_fp4_group<LANES, T>), grid, \
+                     dim3(256), 0, stream, layer_ptrs_dev,                  \
+                     layer_strides_dev, num_layers, block_bytes, bl,        \
+                     ids_dev, dst, footer_bytes)
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype, switch (shift) {
+        case 1: KVC_GATHER_FP4_GROUP(2); break;
+        case 2: KVC_GATHER_FP4_GROUP(4); break;
+        case 3: KVC_GATHER_FP4_GROUP(8); break;
+        default: KVC_GATHER_FP4_GROUP(16); break;
+      });
+#undef KVC_GATHER_FP4_GROUP
+  return hipGetLastError();
+}
+
+extern "C" hipError_t kvc_launch_scatter_fp4_group(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, int group_size,
+    const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
+    const uint8_t* src, hipStream_t stream, uint32_t footer_bytes,
+    int kv_dtype) {
+  const int shift = fp4_group_lane_shift(block_bytes, group_size);
+  if (shift < 0) return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = copy_grid(tiles, block_bytes);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_scatter_fp4_group<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, shift, bl, ids_dev, src, footer_bytes));
+  return hipGetLastError();
+}
+
 
 // ---- per-record checksums ----------------------------------------------------
 // EngineConfig::checksum appends a 16-byte footer to every tile record:

@@ -24,10 +24,15 @@ class OffloadEngineConfig:
     # raw | fp8_e4m3 (16-bit float pages -> fp8 + one scale per (block,
     # layer) tile)
     # | fp8_e4m3_group (fp8 + one scale per fp8_group_size elements)
+    # | fp4_e2m1_group (4-bit e2m1 codes, two per byte, + one scale per
+    #   fp4_group_size elements; lossy at 4 bits, model quality unmeasured)
     serialize: str = "raw"
     # elements per scale for fp8_e4m3_group (set it to head_dim); one of
     # 64/128/256/512, ignored by the other modes
     fp8_group_size: int = 128
+    # elements per scale for fp4_e2m1_group; one of 16/32/64/128, ignored by
+    # the other modes
+    fp4_group_size: int = 32
     host_cache_bytes: int = 0  # pinned-DRAM cache tier (0 = off)
     write_policy: str = "through"  # through | back (flush async via DRAM tier)
     direct_io: bool = False    # O_DIRECT for NVMe (auto-fallback elsewhere)
@@ -38,14 +43,16 @@ class OffloadEngineConfig:
     checksum: bool = False
     device: int = 0
     staging_budget_bytes: int = DEFAULT_STAGING_BUDGET_BYTES
-    # page format the fp8 modes convert from/to: auto | bfloat16 | float16.
+    # page format the fp8 and fp4 modes convert from/to: auto | bfloat16 |
+    # float16.
     # auto = float16 if every KV tensor is torch.float16, else bfloat16; an
     # explicit value covers opaque uint8 views. Ignored by serialize="raw".
     kv_dtype: str = "auto"
 
 
-SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group")
+SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group", "fp4_e2m1_group")
 FP8_GROUP_SIZES = (64, 128, 256, 512)
+FP4_GROUP_SIZES = (16, 32, 64, 128)
 CHECKSUM_FOOTER_BYTES = 16
 CHECKSUM_MAGIC = 0x5343564B  # the bytes "KVCS"
 # suffix of the FileMapper dtype tag that keeps checksummed files apart
@@ -55,7 +62,8 @@ KV_DTYPES = ("bfloat16", "float16")
 
 def resolve_kv_dtype(groups: Sequence[Sequence], kv_dtype: str = "auto",
                      fp8: bool = True) -> str:
-    """Page format the fp8 codec converts with: "bfloat16" or "float16".
+    """Page format the fp8 and fp4 codecs convert with: "bfloat16" or
+    "float16".
 
     ``auto`` is float16 if every KV tensor is ``torch.float16`` and bfloat16
     otherwise (bf16 tensors, and the opaque uint8 views of bf16 bits that
@@ -64,7 +72,8 @@ def resolve_kv_dtype(groups: Sequence[Sequence], kv_dtype: str = "auto",
     when ``fp8`` is true, for an engine that mixes float16 and bfloat16
     tensors or an explicit value that contradicts a tensor's own 16-bit
     float dtype (either direction). ``fp8=False`` (serialize="raw") never
-    converts, so nothing is checked beyond the spelling."""
+    converts, so nothing is checked beyond the spelling; every other mode,
+    fp4_e2m1_group included, is a converting mode and passes ``fp8=True``."""
     import torch
 
     if kv_dtype not in ("auto",) + KV_DTYPES:
@@ -91,20 +100,35 @@ def resolve_kv_dtype(groups: Sequence[Sequence], kv_dtype: str = "auto",
 
 
 def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
-                      group: int = 0, checksum: bool = False) -> int:
+                      group: int = 0, checksum: bool = False,
+                      fp4_group_size: int = 32) -> int:
     """Bytes one (block, layer) tile occupies in a file/object/slab.
 
     raw: block_bytes. fp8_e4m3: n + 4 (n = block_bytes/2 fp8 bytes, one f32
     scale). fp8_e4m3_group: n + 4*n/G (one f32 scale per G elements).
-    checksum=True adds the 16-byte footer (sum u64, magic, payload bytes).
-    Raises ValueError for an unknown mode, a group size outside
-    FP8_GROUP_SIZES, or a KV group whose tile G does not divide.
+    fp4_e2m1_group: n/2 + 4*n/G with G = fp4_group_size (two e2m1 codes per
+    byte). checksum=True adds the 16-byte footer (sum u64, magic, payload
+    bytes). Raises ValueError for an unknown mode, a group size outside
+    FP8_GROUP_SIZES (FP4_GROUP_SIZES for fp4), or a KV group whose tile G
+    does not divide.
     """
     footer = CHECKSUM_FOOTER_BYTES if checksum else 0
     if serialize == "raw":
         return block_bytes + footer
     if serialize == "fp8_e4m3":
         return block_bytes // 2 + 4 + footer
+    if serialize == "fp4_e2m1_group":
+        if fp4_group_size not in FP4_GROUP_SIZES:
+            raise ValueError(
+                f"fp4_group_size must be one of {FP4_GROUP_SIZES}, "
+                f"got {fp4_group_size}")
+        n = block_bytes // 2
+        if block_bytes % 16 != 0 or n % fp4_group_size != 0:
+            raise ValueError(
+                f"KV group {group}: block_bytes={block_bytes} holds {n} "
+                f"16-bit elements, not a multiple of "
+                f"fp4_group_size={fp4_group_size}")
+        return n // 2 + 4 * (n // fp4_group_size) + footer
     if serialize != "fp8_e4m3_group":
         raise ValueError(
             f"serialize must be one of {'|'.join(SERIALIZE_MODES)}, "
@@ -183,10 +207,10 @@ class TorchOffloadEngine:
             # canonical layouts are dense so stride == payload
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
             footer = CHECKSUM_FOOTER_BYTES if config.checksum else 0
-            if config.serialize == "fp8_e4m3_group":
+            if config.serialize in ("fp8_e4m3_group", "fp4_e2m1_group"):
                 record_bytes = tile_record_bytes(
                     config.serialize, bb, config.fp8_group_size, gi,
-                    config.checksum)
+                    config.checksum, config.fp4_group_size)
             else:
                 record_bytes = footer + (
                     bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb)
@@ -241,6 +265,7 @@ class TorchOffloadEngine:
             fp8_group_size=config.fp8_group_size,
             checksum=config.checksum,
             kv_dtype=self.kv_dtype,
+            fp4_group_size=config.fp4_group_size,
         )
         del stream
         # keep tensor refs: the native engine holds raw pointers
@@ -303,7 +328,8 @@ class TorchOffloadEngine:
         first n_blocks' packed bytes, or None on a cache miss / short
         entry. The payload layout matches the file layout (raw gather
         layout, per-tile fp8 records when serialize="fp8_e4m3", group-scaled
-        fp8 records when serialize="fp8_e4m3_group"). With checksum=True
+        fp8 records when serialize="fp8_e4m3_group", group-scaled fp4
+        records when serialize="fp4_e2m1_group"). With checksum=True
         every record in the returned slab still carries its 16-byte footer
         (record stride = group_geometry[group]["record_bytes"]); the slab is
         handed out as stored, it is not verified here."""

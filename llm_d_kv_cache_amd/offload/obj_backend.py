@@ -30,15 +30,17 @@ class ObjStorageConfig:
     bucket: str = "kvcache"
     io_threads: int = 8
     timeout_s: float = 30.0
-    # raw | fp8_e4m3 | fp8_e4m3_group (via the native codec kernels)
+    # raw | fp8_e4m3 | fp8_e4m3_group | fp4_e2m1_group (via the native codec
+    # kernels)
     serialize: str = "raw"
     fp8_group_size: int = 128  # elements per scale, fp8_e4m3_group only
+    fp4_group_size: int = 32  # elements per scale, fp4_e2m1_group only
     # AWS SigV4 credentials; leave access_key empty for anonymous access.
     access_key: str = ""
     secret_key: str = ""
     session_token: str = ""
     region: str = "us-east-1"
-    # page format of the fp8 modes: auto | bfloat16 | float16, resolved like
+    # page format of the fp8 and fp4 modes: auto | bfloat16 | float16, resolved like
     # OffloadEngineConfig.kv_dtype (offload.engine.resolve_kv_dtype)
     kv_dtype: str = "auto"
 
@@ -173,15 +175,18 @@ class ObjStorageEngine:
         native_groups = []
         self.group_geometry: List[dict] = []
         self._fp8_group = config.serialize == "fp8_e4m3_group"
-        self._group_size = config.fp8_group_size
+        self._fp4_group = config.serialize == "fp4_e2m1_group"
+        self._group_size = (config.fp4_group_size if self._fp4_group
+                            else config.fp8_group_size)
         for gi, g in enumerate(groups):
             ptrs = [t.data_ptr() for t in g]
             strides = [t.stride(0) * t.element_size() for t in g]
             bb = strides[0]
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
-            if self._fp8_group:
-                record = tile_record_bytes(config.serialize, bb,
-                                           config.fp8_group_size, gi)
+            if self._fp8_group or self._fp4_group:
+                record = tile_record_bytes(
+                    config.serialize, bb, config.fp8_group_size, gi,
+                    fp4_group_size=config.fp4_group_size)
             else:
                 record = bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb
             self.group_geometry.append(
@@ -205,6 +210,9 @@ class ObjStorageEngine:
     # ---- engine surface -----------------------------------------------------
 
     def _packed(self, group: int, n_blocks: int) -> int:
+        if self._fp4_group:
+            return self._copier.packed_bytes_fp4_group(group, n_blocks,
+                                                       self._group_size)
         if self._fp8_group:
             return self._copier.packed_bytes_fp8_group(group, n_blocks,
                                                        self._group_size)
@@ -229,7 +237,11 @@ class ObjStorageEngine:
                                     device="cuda")
             stream = self._torch.cuda.Stream()
             with self._torch.cuda.stream(stream):
-                if self._fp8_group:
+                if self._fp4_group:
+                    self._copier.gather_fp4_group(group, ids, dev.data_ptr(),
+                                                  self._group_size,
+                                                  stream.cuda_stream)
+                elif self._fp8_group:
                     self._copier.gather_fp8_group(group, ids, dev.data_ptr(),
                                                   self._group_size,
                                                   stream.cuda_stream)
@@ -245,7 +257,10 @@ class ObjStorageEngine:
             stream.synchronize()
         else:
             host = self._slab(group, len(ids))
-            if self._fp8_group:
+            if self._fp4_group:
+                self._copier.gather_fp4_group(group, ids, host.data_ptr(),
+                                              self._group_size, 0)
+            elif self._fp8_group:
                 self._copier.gather_fp8_group(group, ids, host.data_ptr(),
                                               self._group_size, 0)
             elif self._fp8:
@@ -263,7 +278,11 @@ class ObjStorageEngine:
         if len(data) != len(ids) * rec:
             raise IOError(f"short object read for {key}")
         host = self._torch.frombuffer(bytearray(data), dtype=self._torch.uint8)
-        if self._fp8_group:
+        if self._fp4_group:
+            def scatter(group, ids, src, stream):
+                self._copier.scatter_fp4_group(group, ids, src,
+                                               self._group_size, stream)
+        elif self._fp8_group:
             def scatter(group, ids, src, stream):
                 self._copier.scatter_fp8_group(group, ids, src,
                                                self._group_size, stream)

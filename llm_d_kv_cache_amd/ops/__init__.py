@@ -14,10 +14,17 @@ built from, for embedding in other MI355X services.
   (64/128/256/512; set it to head_dim) instead of one per tile. The gather
   is a single pass — the group amax is an in-wave butterfly — and needs no
   scratch. serialize="fp8_e4m3_group" rides these kernels.
-- page format: both fp8 families convert bf16 or fp16 pages. The copier is
+- group-scaled fp4: gather_fp4_group / scatter_fp4_group (sized by
+  packed_bytes_fp4_group) write OCP e2m1 codes, two per byte, with one f32
+  scale per group_size elements (16/32/64/128, default 32): records of
+  n/2 + 4n/G bytes, a quarter to a third of the bf16 page. Same single-pass
+  shape as the fp8-group pair, no scratch. Lossy at 4 bits; the effect on
+  model quality has not been measured. serialize="fp4_e2m1_group" rides
+  these kernels.
+- page format: the fp8 families and the fp4 pair convert bf16 or fp16 pages. The copier is
   built for one format (block_copier(..., kv_dtype="auto"): float16 if
   every page tensor is torch.float16, else bfloat16; pass "float16" /
-  "bfloat16" for opaque uint8 views) and every fp8 method follows it. The
+  "bfloat16" for opaque uint8 views) and every fp8/fp4 method follows it. The
   records are format-free, so the two ends of a transfer need not agree.
 - record checksums: packed_bytes*/gather*/scatter* take checksum=True to
   leave a 16-byte footer behind every record; seal_records(ptr, tiles,
@@ -34,8 +41,8 @@ def block_copier(groups: Sequence[Sequence], device: Optional[int] = None,
                  kv_dtype: str = "auto"):
     """BlockCopier over torch page tensors (GPU or CPU twins).
 
-    kv_dtype (auto | bfloat16 | float16) is the page format every fp8 method
-    of the copier converts with; see offload.engine.resolve_kv_dtype."""
+    kv_dtype (auto | bfloat16 | float16) is the page format every fp8 and
+    fp4 method of the copier converts with; see offload.engine.resolve_kv_dtype."""
     from .. import ensure_offload_native
     from ..offload.engine import resolve_kv_dtype
 

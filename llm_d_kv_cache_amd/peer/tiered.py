@@ -30,13 +30,17 @@ def make_dram_lookup(engine, mapper):
     with serialize="fp8_e4m3_group" keeps group-scaled records in its DRAM
     tier, which the wire cannot label, so its lookup reports a miss every
     time (logged once) and pulls fall through to the storage tier. The same
-    holds for an engine with checksum=True: its DRAM-tier records carry
+    holds for serialize="fp4_e2m1_group" (the wire has no fp4 format
+    either) and for an engine with checksum=True: its DRAM-tier records carry
     16-byte footers the wire does not understand."""
     grouped = engine.config.serialize == "fp8_e4m3_group"
-    if grouped or getattr(engine.config, "checksum", False):
+    fp4 = engine.config.serialize == "fp4_e2m1_group"
+    if grouped or fp4 or getattr(engine.config, "checksum", False):
         warned = []
         why = ("serialize='fp8_e4m3_group': the peer wire has no "
                "group-scaled fp8 format" if grouped else
+               "serialize='fp4_e2m1_group': the peer wire has no "
+               "group-scaled fp4 format" if fp4 else
                "checksum=True: the peer wire does not carry record footers")
 
         def never(chunk_hash, group, n_blocks):
