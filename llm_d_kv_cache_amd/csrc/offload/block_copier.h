@@ -9,9 +9,10 @@
 // bytes alone; seal_records() then fills the footers of any such slab and
 // verify_records() checks them.
 //
-// kv_dtype (bf16 by default) is the format of the 16-bit pages; every fp8
-// and fp4 method of the copier converts with it, the raw ones never look at
-// it.
+// kv_dtype (bf16 by default) is the format of the pages; every fp8 and fp4
+// method of the copier converts with it, the raw ones never look at it. A
+// copier over fp8 (e4m3fn) pages has the raw and the fp4 methods only: its
+// *_fp8 and *_fp8_group methods throw, the pages already are fp8.
 #pragma once
 
 #include <mutex>
@@ -61,6 +62,7 @@ class BlockCopier {
   // fp8 e4m3 record size: block_bytes/2 payload + f32 scale per tile.
   size_t packed_bytes_fp8(int group, size_t n_blocks,
                           bool checksum = false) const {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     return n_blocks * g.layer_ptrs.size() *
            (g.block_bytes / 2 + 4 + footer(checksum));
@@ -126,6 +128,7 @@ class BlockCopier {
   // fp8_scratch_bytes(). Host mode uses the software codec.
   void gather_fp8(int group, const std::vector<int32_t>& ids, void* dst,
                   void* scratch, uintptr_t stream, bool checksum = false) {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     check_ids(ids, g);
     if (!gpu_mode_) {
@@ -146,6 +149,7 @@ class BlockCopier {
   // Dequantize + scatter from an fp8 record slab.
   void scatter_fp8(int group, const std::vector<int32_t>& ids, const void* src,
                    uintptr_t stream, bool checksum = false) {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     check_ids(ids, g);
     if (!gpu_mode_) {
@@ -167,6 +171,7 @@ class BlockCopier {
   // per group_size elements, per tile.
   size_t packed_bytes_fp8_group(int group, size_t n_blocks, int group_size,
                                 bool checksum = false) const {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     check_group_size(g, group_size);
     return n_blocks * g.layer_ptrs.size() *
@@ -180,6 +185,7 @@ class BlockCopier {
   void gather_fp8_group(int group, const std::vector<int32_t>& ids, void* dst,
                         int group_size, uintptr_t stream,
                         bool checksum = false) {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     check_ids(ids, g);
     check_group_size(g, group_size);
@@ -203,6 +209,7 @@ class BlockCopier {
   void scatter_fp8_group(int group, const std::vector<int32_t>& ids,
                          const void* src, int group_size, uintptr_t stream,
                          bool checksum = false) {
+    check_not_fp8_pages();
     const GroupDesc& g = groups_.at(group);
     check_ids(ids, g);
     check_group_size(g, group_size);
@@ -222,15 +229,16 @@ class BlockCopier {
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
-  // Group-scaled fp4 (e2m1) record size: block_bytes/4 code bytes + one f32
-  // scale per group_size elements, per tile.
+  // Group-scaled fp4 (e2m1) record size: n/2 code bytes + one f32 scale per
+  // group_size elements, per tile; n = block_bytes/2 elements for 16-bit
+  // pages, block_bytes for fp8 pages.
   size_t packed_bytes_fp4_group(int group, size_t n_blocks, int group_size,
                                 bool checksum = false) const {
     const GroupDesc& g = groups_.at(group);
     check_fp4_group_size(g, group_size);
     return n_blocks * g.layer_ptrs.size() *
-           (StorageOffloadEngine::fp4_group_record_bytes(g.block_bytes,
-                                                         group_size) +
+           (StorageOffloadEngine::fp4_group_record_bytes(
+                g.block_bytes, group_size, kv_dtype_) +
             footer(checksum));
   }
 
@@ -375,16 +383,25 @@ class BlockCopier {
           std::to_string(group_size));
   }
 
-  static void check_fp4_group_size(const GroupDesc& g, int group_size) {
+  void check_fp4_group_size(const GroupDesc& g, int group_size) const {
     if (!fp4_group_size_ok(group_size))
       throw std::invalid_argument(
           "fp4 group_size must be 16, 32, 64 or 128 (got " +
           std::to_string(group_size) + ")");
-    if (g.block_bytes % 16 != 0 || (g.block_bytes / 2) % group_size != 0)
+    const uint64_t n = kv_tile_elems(g.block_bytes, kv_dtype_);
+    if (g.block_bytes % 16 != 0 || n % group_size != 0)
       throw std::invalid_argument(
-          "block_bytes/2 = " + std::to_string(g.block_bytes / 2) +
-          " elements is not a multiple of fp4 group_size " +
+          std::string(kv_dtype_ == KvDtype::kFp8E4M3 ? "block_bytes = "
+                                                     : "block_bytes/2 = ") +
+          std::to_string(n) + " elements is not a multiple of fp4 group_size " +
           std::to_string(group_size));
+  }
+
+  void check_not_fp8_pages() const {
+    if (kv_dtype_ == KvDtype::kFp8E4M3)
+      throw std::invalid_argument(
+          "kv_dtype float8_e4m3fn: the pages already are fp8, the fp8 methods "
+          "do not apply; use the raw or the fp4_group methods");
   }
 
   void host_copy(const GroupDesc& g, const std::vector<int32_t>& ids,

@@ -67,7 +67,9 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
 extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
     int, const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
-// group-scaled fp4 (e2m1): same argument lists as the fp8-group pair
+// group-scaled fp4 (e2m1): same argument lists as the fp8-group pair; the
+// only launchers that also take KvDtype::kFp8E4M3 pages (block_bytes elements
+// per tile instead of block_bytes/2)
 extern "C" hipError_t kvc_launch_gather_fp4_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
     int, const int32_t*, uint8_t*, hipStream_t, uint32_t, int);
@@ -114,17 +116,26 @@ enum class CopyPath { kStaged, kZeroCopy, kHostMemcpy };
 // [ n/2 code bytes | n/G f32 scales ].
 enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group, kFp4E2M1Group };
 
-// Format of the 16-bit KV pages the fp8 and fp4 modes read on store and
-// write on load (raw copies never look at it). The records are format-free; only the
+// Format of the KV pages the fp8 and fp4 modes read on store and write on
+// load (raw copies never look at it). The records are format-free; only the
 // page <-> f32 conversions differ. The values are the kv_dtype argument of
-// the fp8 launchers in kernels.hip.
-enum class KvDtype : int { kBf16 = 0, kFp16 = 1 };
+// the fp8 and fp4 launchers in kernels.hip. kFp8E4M3 pages (OCP e4m3fn, one
+// byte per element) are a source of kFp4E2M1Group only: the fp8 modes have
+// nothing to narrow and their launchers reject the value.
+enum class KvDtype : int { kBf16 = 0, kFp16 = 1, kFp8E4M3 = 2 };
 
 inline KvDtype parse_kv_dtype(const std::string& s) {
   if (s == "bfloat16") return KvDtype::kBf16;
   if (s == "float16") return KvDtype::kFp16;
-  throw std::invalid_argument("kv_dtype must be bfloat16|float16 (got '" + s +
-                              "')");
+  if (s == "float8_e4m3fn") return KvDtype::kFp8E4M3;
+  throw std::invalid_argument(
+      "kv_dtype must be bfloat16|float16|float8_e4m3fn (got '" + s + "')");
+}
+
+// Elements in a tile of block_bytes: two bytes each for bf16/fp16 pages, one
+// for fp8 pages.
+inline uint64_t kv_tile_elems(uint64_t block_bytes, KvDtype kv_dtype) {
+  return kv_dtype == KvDtype::kFp8E4M3 ? block_bytes : block_bytes / 2;
 }
 
 inline bool fp8_group_size_ok(int g) {
@@ -250,6 +261,11 @@ class StorageOffloadEngine {
       throw std::invalid_argument(
           "fp8_group_size must be 64, 128, 256 or 512 (got " +
           std::to_string(cfg_.fp8_group_size) + ")");
+    if (cfg_.kv_dtype == KvDtype::kFp8E4M3 &&
+        (grouped || cfg_.serialize == Serialize::kFp8E4M3))
+      throw std::invalid_argument(
+          "kv_dtype float8_e4m3fn: the pages already are fp8, so the fp8 "
+          "serialize modes do not apply; use raw or fp4_e2m1_group");
     const bool fp4 = cfg_.serialize == Serialize::kFp4E2M1Group;
     if (fp4 && !fp4_group_size_ok(cfg_.fp4_group_size))
       throw std::invalid_argument(
@@ -272,10 +288,13 @@ class StorageOffloadEngine {
             std::to_string(g.block_bytes / 2) +
             " elements is not a multiple of fp8_group_size " +
             std::to_string(cfg_.fp8_group_size));
-      if (fp4 && (g.block_bytes / 2) % cfg_.fp4_group_size != 0)
+      if (fp4 &&
+          kv_tile_elems(g.block_bytes, cfg_.kv_dtype) % cfg_.fp4_group_size != 0)
         throw std::invalid_argument(
-            "group " + std::to_string(gi) + ": block_bytes/2 = " +
-            std::to_string(g.block_bytes / 2) +
+            "group " + std::to_string(gi) + ": " +
+            (cfg_.kv_dtype == KvDtype::kFp8E4M3 ? "block_bytes = "
+                                                : "block_bytes/2 = ") +
+            std::to_string(kv_tile_elems(g.block_bytes, cfg_.kv_dtype)) +
             " elements is not a multiple of fp4_group_size " +
             std::to_string(cfg_.fp4_group_size));
       if (g.layer_ptrs.size() != g.layer_strides.size())
@@ -637,7 +656,8 @@ class StorageOffloadEngine {
       case Serialize::kFp8E4M3Group:
         return fp8_group_record_bytes(g.block_bytes, cfg_.fp8_group_size);
       case Serialize::kFp4E2M1Group:
-        return fp4_group_record_bytes(g.block_bytes, cfg_.fp4_group_size);
+        return fp4_group_record_bytes(g.block_bytes, cfg_.fp4_group_size,
+                                      cfg_.kv_dtype);
       default:
         return g.block_bytes;
     }
@@ -1458,8 +1478,9 @@ class StorageOffloadEngine {
     }
   }
 
-  static size_t fp4_group_record_bytes(uint64_t block_bytes, int group_size) {
-    const size_t n = block_bytes / 2;
+  static size_t fp4_group_record_bytes(uint64_t block_bytes, int group_size,
+                                       KvDtype kv_dtype = KvDtype::kBf16) {
+    const size_t n = kv_tile_elems(block_bytes, kv_dtype);
     return n / 2 + 4 * (n / static_cast<size_t>(group_size));
   }
 
@@ -1472,7 +1493,7 @@ class StorageOffloadEngine {
                                   KvDtype kv_dtype = KvDtype::kBf16) {
     const size_t nl = g.layer_ptrs.size();
     const size_t rec =
-        fp4_group_record_bytes(g.block_bytes, group_size) + footer;
+        fp4_group_record_bytes(g.block_bytes, group_size, kv_dtype) + footer;
     for (size_t bi = 0; bi < ids.size(); ++bi) {
       for (size_t l = 0; l < nl; ++l) {
         uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +
@@ -1571,6 +1592,52 @@ class StorageOffloadEngine {
     }
   }
 
+  // fp4 over fp8 (e4m3fn) pages: n = block_bytes elements of one byte each.
+  // Same arithmetic with x = the exact f32 value of the page byte; the load
+  // rounds the f32 product to e4m3fn with f32_to_fp8_rne, which keeps
+  // subnormals and copies the sign onto a zero magnitude (0x80). NaN page
+  // bytes are out of scope (fmax drops them from amax, as the kernel's
+  // fmaxf does).
+  static void fp4_group_quantize_tile_fp8page(const uint8_t* src,
+                                              size_t block_bytes,
+                                              int group_size, uint8_t* out) {
+    const size_t n = block_bytes;
+    const size_t G = static_cast<size_t>(group_size);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      const uint8_t* x = src + gi * G;
+      float amax = 0.0f;
+      for (size_t i = 0; i < G; ++i)
+        amax = std::max(amax, std::abs(fp8_to_f32(x[i])));
+      if (amax <= 0.0f) amax = 1.0f;
+      const float scale = amax / 6.0f;
+      const float inv = 6.0f / amax;
+      uint8_t* codes = out + gi * G / 2;
+      for (size_t i = 0; i < G; i += 2)
+        codes[i / 2] = static_cast<uint8_t>(
+            f32_to_fp4_rne(fp8_to_f32(x[i]) * inv) |
+            (f32_to_fp4_rne(fp8_to_f32(x[i + 1]) * inv) << 4));
+      std::memcpy(out + n / 2 + 4 * gi, &scale, 4);
+    }
+  }
+
+  static void fp4_group_dequantize_tile_fp8page(const uint8_t* in,
+                                                size_t block_bytes,
+                                                int group_size, uint8_t* dst) {
+    const size_t n = block_bytes;
+    const size_t G = static_cast<size_t>(group_size);
+    for (size_t gi = 0; gi < n / G; ++gi) {
+      float scale;
+      std::memcpy(&scale, in + n / 2 + 4 * gi, 4);
+      const uint8_t* codes = in + gi * G / 2;
+      for (size_t i = 0; i < G; i += 2) {
+        const float p0 = fp4_to_f32(codes[i / 2] & 0xf) * scale;
+        const float p1 = fp4_to_f32(codes[i / 2] >> 4) * scale;
+        dst[gi * G + i] = f32_to_fp8_rne(p0);
+        dst[gi * G + i + 1] = f32_to_fp8_rne(p1);
+      }
+    }
+  }
+
   template <typename T>
   static void fp8_quantize_tile_t(const uint8_t* src, size_t block_bytes,
                          uint8_t* out) {
@@ -1622,7 +1689,9 @@ class StorageOffloadEngine {
   static void fp4_group_quantize_tile(const uint8_t* src, size_t block_bytes,
                                       int group_size, uint8_t* out,
                                       KvDtype kv_dtype) {
-    if (kv_dtype == KvDtype::kFp16)
+    if (kv_dtype == KvDtype::kFp8E4M3)
+      fp4_group_quantize_tile_fp8page(src, block_bytes, group_size, out);
+    else if (kv_dtype == KvDtype::kFp16)
       fp4_group_quantize_tile_t<PageFp16>(src, block_bytes, group_size, out);
     else
       fp4_group_quantize_tile_t<PageBf16>(src, block_bytes, group_size, out);
@@ -1630,7 +1699,9 @@ class StorageOffloadEngine {
   static void fp4_group_dequantize_tile(const uint8_t* in, size_t block_bytes,
                                         int group_size, uint8_t* dst,
                                         KvDtype kv_dtype) {
-    if (kv_dtype == KvDtype::kFp16)
+    if (kv_dtype == KvDtype::kFp8E4M3)
+      fp4_group_dequantize_tile_fp8page(in, block_bytes, group_size, dst);
+    else if (kv_dtype == KvDtype::kFp16)
       fp4_group_dequantize_tile_t<PageFp16>(in, block_bytes, group_size, dst);
     else
       fp4_group_dequantize_tile_t<PageBf16>(in, block_bytes, group_size, dst);

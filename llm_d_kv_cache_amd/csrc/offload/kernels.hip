@@ -951,11 +951,172 @@ __global__ __launch_bounds__(256) void kvc_scatter_fp4_group(
   }
 }
 
+// ---- fp4 records over fp8 (OCP e4m3fn) pages ---------------------------------
+// kv_dtype="float8_e4m3fn": the page already is one byte per element, so a
+// tile holds n = block_bytes elements (not block_bytes/2) and the record is
+//   [ n/2 code bytes | n/G f32 scales ],  n % G == 0,  G in {16, 32, 64, 128}.
+// The arithmetic is the fp4 spec above with x = the exact f32 value of the
+// page byte and the load rounding to e4m3fn: y = RNE_e4m3fn(f32(value(code))
+// * scale), subnormals kept, the sign copied even when the magnitude rounds
+// to zero (-0.0 and negatives that underflow load as 0x80). NaN page bytes
+// (0x7f/0xff) are out of scope.
+//
+// 16 page values per lane: a lane loads 16 B, stores 8 B of codes, and a
+// group is G/16 = 1..8 consecutive lanes (0..3 butterfly steps).
+// copy_grid(tiles, block_bytes) yields exactly block_bytes/16 vectors per
+// tile. Records are multiples of 4 bytes but not of 8 (G=32 at 32-byte
+// tiles: 20 bytes), so the 8-byte code accesses land at 4 mod 8, like the
+// per-tile fp8 kernels' stores.
+
 namespace {
 
-// G -> log2(G/8); -1 for anything but 16/32/64/128 or a tile the group size
-// does not divide.
-inline int fp4_group_lane_shift(uint64_t block_bytes, int group_size) {
+constexpr int kKvFp8E4M3 = 2;
+
+// One dword of page bytes -> its four exact f32 values (v_cvt_pk_f32_fp8).
+__device__ __forceinline__ void fp8_page_unpack4(uint32_t w, float* x) {
+  const kvc_float2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+  const kvc_float2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+  x[0] = lo.x;
+  x[1] = lo.y;
+  x[2] = hi.x;
+  x[3] = hi.y;
+}
+
+// Four f32 products (already rounded to f32) -> one dword of page bytes:
+// v_cvt_pk_fp8_f32, RNE with e4m3 subnormals. The instruction keeps the
+// sign of -0.0 and of a negative that underflows (0x80), which is what the
+// format asks for (measured on an MI355X against the host twin over every
+// value(code) * scale our encoders can write; profiles/
+// fp8_page_fp4_kernels.md), so no fix-up follows it.
+__device__ __forceinline__ uint32_t fp8_page_pack4(float p0, float p1, float p2,
+                                                   float p3) {
+  uint32_t w = 0;
+  // word_sel must be an immediate: unrolled by hand
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(p0, p1, w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(p2, p3, w, true);
+  return w;
+}
+
+}  // namespace
+
+// kLanes = G/16 lanes per group. Same loop as kvc_gather_fp4_group: a
+// WAVE-UNIFORM grid-stride base with a guarded body, so every lane reaches
+// every shuffle; groups are kLanes-aligned runs of v and n % G == 0, so a
+// group is wholly inside the tile or wholly past its end, and the xor
+// butterfly (offsets < kLanes) never leaves it.
+template <int kLanes>
+__global__ __launch_bounds__(256) void kvc_gather_fp4_group_fp8page(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
+  static_assert(kLanes == 1 || kLanes == 2 || kLanes == 4 || kLanes == 8,
+                "group must span 1..8 lanes of one wave");
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes;  // one byte per page element
+  const uint64_t n_groups = n_elems / (16 * kLanes);
+  const uint64_t record = n_elems / 2 + 4 * n_groups + footer_bytes;
+  const uint4* __restrict__ vsrc = reinterpret_cast<const uint4*>(
+      static_cast<const uint8_t*>(layer_ptrs[l]) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  uint8_t* __restrict__ payload = dst + static_cast<uint64_t>(tile) * record;
+  uint2* __restrict__ vout = reinterpret_cast<uint2*>(payload);
+  float* __restrict__ scales = reinterpret_cast<float*>(payload + n_elems / 2);
+  const uint64_t nvec = n_elems / 16;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t vb = static_cast<uint64_t>(blockIdx.y) * blockDim.x +
+                     (threadIdx.x & ~63u);
+       vb < nvec; vb += stride) {
+    const uint64_t v = vb + lane;
+    const bool live = v < nvec;
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (live) w = vsrc[v];
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
+    float x[16];
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      fp8_page_unpack4(dw[j], x + 4 * j);
+      amax = fmaxf(fmaxf(amax, fmaxf(fabsf(x[4 * j]), fabsf(x[4 * j + 1]))),
+                   fmaxf(fabsf(x[4 * j + 2]), fabsf(x[4 * j + 3])));
+    }
+#pragma unroll
+    for (int off = kLanes / 2; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    if (amax <= 0.0f) amax = 1.0f;
+    const float inv_scale = kFp4Max / amax;
+    float lo[8], hi[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      lo[j] = x[j] * inv_scale;
+      hi[j] = x[8 + j] * inv_scale;
+    }
+    uint2 out;
+    out.x = fp4_e2m1_pack8(lo);
+    out.y = fp4_e2m1_pack8(hi);
+    if (live) {
+      vout[v] = out;
+      if ((lane & (kLanes - 1)) == 0) scales[v / kLanes] = amax / kFp4Max;
+    }
+  }
+}
+
+// Sliced dequantize+scatter of fp4 records into fp8 pages: the shape of
+// kvc_scatter_fp4_group at 16 values per lane. A lane reads 8 B of codes and
+// writes 16 page bytes as one dwordx4; its scale is scales[(16 v) / G] =
+// scales[v >> lane_shift] (lane_shift = log2(G/16)).
+__global__ __launch_bounds__(256) void kvc_scatter_fp4_group_fp8page(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, int lane_shift, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint64_t n_elems = block_bytes;
+  const uint64_t nvec = n_elems / 16;
+  const uint64_t record = n_elems / 2 + 4 * (nvec >> lane_shift) + footer_bytes;
+  uint4* __restrict__ vout = reinterpret_cast<uint4*>(
+      static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l]);
+  const uint8_t* __restrict__ payload =
+      src + static_cast<uint64_t>(tile) * record;
+  const uint2* __restrict__ vin = reinterpret_cast<const uint2*>(payload);
+  const float* __restrict__ scales =
+      reinterpret_cast<const float*>(payload + n_elems / 2);
+  const uint64_t stride = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  for (uint64_t v = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
+       v < nvec; v += stride) {
+    const float scale = scales[v >> lane_shift];
+    const uint2 codes = vin[v];
+    // byte_sel must be an immediate: unrolled by hand
+    const kvc_float2 val[8] = {
+        fp4_e2m1_unpack2<0>(codes.x), fp4_e2m1_unpack2<1>(codes.x),
+        fp4_e2m1_unpack2<2>(codes.x), fp4_e2m1_unpack2<3>(codes.x),
+        fp4_e2m1_unpack2<0>(codes.y), fp4_e2m1_unpack2<1>(codes.y),
+        fp4_e2m1_unpack2<2>(codes.y), fp4_e2m1_unpack2<3>(codes.y)};
+    uint4 o;
+    uint32_t* od = reinterpret_cast<uint32_t*>(&o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      od[j] = fp8_page_pack4(val[2 * j].x * scale, val[2 * j].y * scale,
+                             val[2 * j + 1].x * scale, val[2 * j + 1].y * scale);
+    vout[v] = o;
+  }
+}
+
+namespace {
+
+// G -> log2(G / values per lane), 8 values per lane for 16-bit pages and 16
+// for fp8 pages; -1 for anything but 16/32/64/128, a page format the fp4
+// kernels do not read, or a tile the group size does not divide.
+inline int fp4_group_lane_shift(uint64_t block_bytes, int group_size,
+                                int kv_dtype) {
   int shift;
   switch (group_size) {
     case 16: shift = 1; break;
@@ -964,9 +1125,17 @@ inline int fp4_group_lane_shift(uint64_t block_bytes, int group_size) {
     case 128: shift = 4; break;
     default: return -1;
   }
-  if (block_bytes % 16 != 0 ||
-      (block_bytes / 2) % static_cast<uint64_t>(group_size) != 0)
+  if (block_bytes % 16 != 0) return -1;
+  uint64_t n_elems;
+  if (kv_dtype == kKvFp8E4M3) {
+    n_elems = block_bytes;
+    shift -= 1;
+  } else if (kv_dtype == kKvBf16 || kv_dtype == kKvFp16) {
+    n_elems = block_bytes / 2;
+  } else {
     return -1;
+  }
+  if (n_elems % static_cast<uint64_t>(group_size) != 0) return -1;
   return shift;
 }
 
@@ -977,7 +1146,7 @@ extern "C" hipError_t kvc_launch_gather_fp4_group(
     int num_layers, uint64_t block_bytes, int group_size,
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
     uint8_t* dst, hipStream_t stream, uint32_t footer_bytes, int kv_dtype) {
-  const int shift = fp4_group_lane_shift(block_bytes, group_size);
+  const int shift = fp4_group_lane_shift(block_bytes, group_size, kv_dtype);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
   if (ids_dev == nullptr) {
@@ -986,6 +1155,21 @@ extern "C" hipError_t kvc_launch_gather_fp4_group(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
+  if (kv_dtype == kKvFp8E4M3) {
+#define KVC_GATHER_FP4_FP8PAGE(LANES)                                        \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(kvc_gather_fp4_group_fp8page<LANES>),   \
+                     grid, dim3(256), 0, stream, layer_ptrs_dev,             \
+                     layer_strides_dev, num_layers, block_bytes, bl,         \
+                     ids_dev, dst, footer_bytes)
+    switch (shift) {
+      case 0: KVC_GATHER_FP4_FP8PAGE(1); break;
+      case 1: KVC_GATHER_FP4_FP8PAGE(2); break;
+      case 2: KVC_GATHER_FP4_FP8PAGE(4); break;
+      default: KVC_GATHER_FP4_FP8PAGE(8); break;
+    }
+#undef KVC_GATHER_FP4_FP8PAGE
+    return hipGetLastError();
+  }
 #define KVC_GATHER_FP4_GROUP(LANES)                                         \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(kvc_gather_fp4_group<LANES, T>), grid, \
                      dim3(256), 0, stream, layer_ptrs_dev,                  \
@@ -1008,7 +1192,7 @@ extern "C" hipError_t kvc_launch_scatter_fp4_group(
     const int32_t* block_ids, int num_blocks, const int32_t* ids_dev,
     const uint8_t* src, hipStream_t stream, uint32_t footer_bytes,
     int kv_dtype) {
-  const int shift = fp4_group_lane_shift(block_bytes, group_size);
+  const int shift = fp4_group_lane_shift(block_bytes, group_size, kv_dtype);
   if (shift < 0) return hipErrorInvalidValue;
   BlockList bl;
   if (ids_dev == nullptr) {
@@ -1017,6 +1201,12 @@ extern "C" hipError_t kvc_launch_scatter_fp4_group(
   }
   uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
   dim3 grid = copy_grid(tiles, block_bytes);
+  if (kv_dtype == kKvFp8E4M3) {
+    hipLaunchKernelGGL(kvc_scatter_fp4_group_fp8page, grid, dim3(256), 0,
+                       stream, layer_ptrs_dev, layer_strides_dev, num_layers,
+                       block_bytes, shift, bl, ids_dev, src, footer_bytes);
+    return hipGetLastError();
+  }
   KVC_WITH_PAGE_TYPE(
       kv_dtype,
       hipLaunchKernelGGL(kvc_scatter_fp4_group<T>, grid, dim3(256), 0, stream,

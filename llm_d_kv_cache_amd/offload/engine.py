@@ -44,9 +44,12 @@ class OffloadEngineConfig:
     device: int = 0
     staging_budget_bytes: int = DEFAULT_STAGING_BUDGET_BYTES
     # page format the fp8 and fp4 modes convert from/to: auto | bfloat16 |
-    # float16.
-    # auto = float16 if every KV tensor is torch.float16, else bfloat16; an
-    # explicit value covers opaque uint8 views. Ignored by serialize="raw".
+    # float16 | float8_e4m3fn.
+    # auto = float16 if every KV tensor is torch.float16, float8_e4m3fn if
+    # every one is torch.float8_e4m3fn, else bfloat16; an explicit value
+    # covers opaque uint8 views. float8_e4m3fn pages (an fp8 KV cache) are a
+    # source of fp4_e2m1_group only; the fp8 modes raise on them. Ignored by
+    # serialize="raw".
     kv_dtype: str = "auto"
 
 
@@ -57,61 +60,94 @@ CHECKSUM_FOOTER_BYTES = 16
 CHECKSUM_MAGIC = 0x5343564B  # the bytes "KVCS"
 # suffix of the FileMapper dtype tag that keeps checksummed files apart
 CHECKSUM_DTYPE_SUFFIX = "+ck"
-KV_DTYPES = ("bfloat16", "float16")
+KV_DTYPES = ("bfloat16", "float16", "float8_e4m3fn")
+# bytes per page element
+KV_DTYPE_BYTES = {"bfloat16": 2, "float16": 2, "float8_e4m3fn": 1}
 
 
 def resolve_kv_dtype(groups: Sequence[Sequence], kv_dtype: str = "auto",
                      fp8: bool = True) -> str:
-    """Page format the fp8 and fp4 codecs convert with: "bfloat16" or
-    "float16".
+    """Page format the fp8 and fp4 codecs convert with: "bfloat16",
+    "float16" or "float8_e4m3fn".
 
-    ``auto`` is float16 if every KV tensor is ``torch.float16`` and bfloat16
+    ``auto`` is float16 if every KV tensor is ``torch.float16``,
+    float8_e4m3fn if every one is ``torch.float8_e4m3fn``, and bfloat16
     otherwise (bf16 tensors, and the opaque uint8 views of bf16 bits that
-    predate this option). An explicit value covers uint8 views of fp16
-    pages. Raises ValueError for a value outside auto|bfloat16|float16, and,
-    when ``fp8`` is true, for an engine that mixes float16 and bfloat16
-    tensors or an explicit value that contradicts a tensor's own 16-bit
-    float dtype (either direction). ``fp8=False`` (serialize="raw") never
-    converts, so nothing is checked beyond the spelling; every other mode,
-    fp4_e2m1_group included, is a converting mode and passes ``fp8=True``."""
+    predate this option). An explicit value covers uint8 views of fp16 or
+    fp8 pages. Raises ValueError for a value outside
+    auto|bfloat16|float16|float8_e4m3fn, and, when ``fp8`` is true, for an
+    engine that mixes float16, bfloat16 and float8_e4m3fn tensors, an
+    explicit value that contradicts a tensor's own float dtype (either
+    direction), or a ``torch.float8_e4m3fnuz`` / ``torch.float8_e5m2``
+    tensor (no codec reads those pages). ``fp8=False`` (serialize="raw")
+    never converts, so nothing is checked beyond the spelling; every other
+    mode, fp4_e2m1_group included, is a converting mode and passes
+    ``fp8=True``."""
     import torch
 
     if kv_dtype not in ("auto",) + KV_DTYPES:
         raise ValueError(
             f"kv_dtype must be one of auto|{'|'.join(KV_DTYPES)}, "
             f"got {kv_dtype!r}")
-    names = {torch.float16: "float16", torch.bfloat16: "bfloat16"}
+    names = {torch.float16: "float16", torch.bfloat16: "bfloat16",
+             torch.float8_e4m3fn: "float8_e4m3fn"}
+    unsupported = (torch.float8_e4m3fnuz, torch.float8_e5m2)
     tensors = [t for g in groups for t in g]
     seen = {names[t.dtype] for t in tensors if t.dtype in names}
     if fp8:
+        for t in tensors:
+            if t.dtype in unsupported:
+                raise ValueError(
+                    f"KV tensors of dtype {t.dtype} cannot be converted: the "
+                    "only fp8 page format is float8_e4m3fn (OCP); use "
+                    "serialize='raw'")
         if len(seen) > 1:
             raise ValueError(
-                "KV tensors mix float16 and bfloat16; the fp8 codec needs one "
-                "page format per engine")
+                f"KV tensors mix {' and '.join(sorted(seen))}; the fp8 and "
+                "fp4 codecs need one page format per engine")
         if kv_dtype != "auto" and seen and kv_dtype not in seen:
             raise ValueError(
                 f"kv_dtype={kv_dtype!r} contradicts KV tensors of dtype "
                 f"torch.{next(iter(seen))}")
     if kv_dtype != "auto":
         return kv_dtype
-    if tensors and all(t.dtype == torch.float16 for t in tensors):
-        return "float16"
+    for dtype in (torch.float16, torch.float8_e4m3fn):
+        if tensors and all(t.dtype == dtype for t in tensors):
+            return names[dtype]
     return "bfloat16"
+
+
+def check_serialize_kv_dtype(serialize: str, kv_dtype: str) -> None:
+    """float8_e4m3fn pages already are fp8: the fp8 modes raise ValueError on
+    them. ``kv_dtype`` is a resolved value (resolve_kv_dtype)."""
+    if kv_dtype == "float8_e4m3fn" and serialize in ("fp8_e4m3",
+                                                     "fp8_e4m3_group"):
+        raise ValueError(
+            f"serialize={serialize!r} does not apply to kv_dtype="
+            "'float8_e4m3fn' pages, they already are fp8; use 'raw' or "
+            "'fp4_e2m1_group'")
 
 
 def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
                       group: int = 0, checksum: bool = False,
-                      fp4_group_size: int = 32) -> int:
+                      fp4_group_size: int = 32, *,
+                      kv_dtype: str = "bfloat16") -> int:
     """Bytes one (block, layer) tile occupies in a file/object/slab.
 
     raw: block_bytes. fp8_e4m3: n + 4 (n = block_bytes/2 fp8 bytes, one f32
     scale). fp8_e4m3_group: n + 4*n/G (one f32 scale per G elements).
     fp4_e2m1_group: n/2 + 4*n/G with G = fp4_group_size (two e2m1 codes per
-    byte). checksum=True adds the 16-byte footer (sum u64, magic, payload
-    bytes). Raises ValueError for an unknown mode, a group size outside
-    FP8_GROUP_SIZES (FP4_GROUP_SIZES for fp4), or a KV group whose tile G
-    does not divide.
+    byte). kv_dtype is the resolved page format: with "float8_e4m3fn" a tile
+    holds n = block_bytes elements, so fp4_e2m1_group gives block_bytes/2 +
+    4*block_bytes/G; the fp8 modes raise on such pages. checksum=True adds
+    the 16-byte footer (sum u64, magic, payload bytes). Raises ValueError
+    for an unknown mode or page format, a group size outside FP8_GROUP_SIZES
+    (FP4_GROUP_SIZES for fp4), or a KV group whose tile G does not divide.
     """
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(
+            f"kv_dtype must be one of {'|'.join(KV_DTYPES)}, got {kv_dtype!r}")
+    check_serialize_kv_dtype(serialize, kv_dtype)
     footer = CHECKSUM_FOOTER_BYTES if checksum else 0
     if serialize == "raw":
         return block_bytes + footer
@@ -122,11 +158,12 @@ def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
             raise ValueError(
                 f"fp4_group_size must be one of {FP4_GROUP_SIZES}, "
                 f"got {fp4_group_size}")
-        n = block_bytes // 2
+        width = KV_DTYPE_BYTES[kv_dtype]
+        n = block_bytes // width
         if block_bytes % 16 != 0 or n % fp4_group_size != 0:
             raise ValueError(
                 f"KV group {group}: block_bytes={block_bytes} holds {n} "
-                f"16-bit elements, not a multiple of "
+                f"{8 * width}-bit elements, not a multiple of "
                 f"fp4_group_size={fp4_group_size}")
         return n // 2 + 4 * (n // fp4_group_size) + footer
     if serialize != "fp8_e4m3_group":
@@ -188,9 +225,11 @@ class TorchOffloadEngine:
                 "use copy_path='host' for CPU tensors"
             )
 
-        # resolved page format of the fp8 modes ("bfloat16" | "float16")
+        # resolved page format of the fp8 and fp4 modes ("bfloat16" |
+        # "float16" | "float8_e4m3fn")
         self.kv_dtype = resolve_kv_dtype(
             groups, config.kv_dtype, fp8=config.serialize != "raw")
+        check_serialize_kv_dtype(config.serialize, self.kv_dtype)
 
         native_groups = []
         self.group_geometry: List[dict] = []
@@ -210,7 +249,8 @@ class TorchOffloadEngine:
             if config.serialize in ("fp8_e4m3_group", "fp4_e2m1_group"):
                 record_bytes = tile_record_bytes(
                     config.serialize, bb, config.fp8_group_size, gi,
-                    config.checksum, config.fp4_group_size)
+                    config.checksum, config.fp4_group_size,
+                    kv_dtype=self.kv_dtype)
             else:
                 record_bytes = footer + (
                     bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb)

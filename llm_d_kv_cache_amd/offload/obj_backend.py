@@ -40,7 +40,8 @@ class ObjStorageConfig:
     secret_key: str = ""
     session_token: str = ""
     region: str = "us-east-1"
-    # page format of the fp8 and fp4 modes: auto | bfloat16 | float16, resolved like
+    # page format of the fp8 and fp4 modes: auto | bfloat16 | float16 |
+    # float8_e4m3fn (fp4_e2m1_group and raw only), resolved like
     # OffloadEngineConfig.kv_dtype (offload.engine.resolve_kv_dtype)
     kv_dtype: str = "auto"
 
@@ -164,7 +165,8 @@ class ObjStorageEngine:
         import torch
 
         from .. import ensure_offload_native
-        from .engine import resolve_kv_dtype, tile_record_bytes
+        from .engine import (check_serialize_kv_dtype, resolve_kv_dtype,
+                             tile_record_bytes)
 
         ko = ensure_offload_native()
         self._torch = torch
@@ -172,6 +174,7 @@ class ObjStorageEngine:
         self.gpu_mode = groups[0][0].is_cuda
         self.kv_dtype = resolve_kv_dtype(
             groups, config.kv_dtype, fp8=config.serialize != "raw")
+        check_serialize_kv_dtype(config.serialize, self.kv_dtype)
         native_groups = []
         self.group_geometry: List[dict] = []
         self._fp8_group = config.serialize == "fp8_e4m3_group"
@@ -186,7 +189,8 @@ class ObjStorageEngine:
             if self._fp8_group or self._fp4_group:
                 record = tile_record_bytes(
                     config.serialize, bb, config.fp8_group_size, gi,
-                    fp4_group_size=config.fp4_group_size)
+                    fp4_group_size=config.fp4_group_size,
+                    kv_dtype=self.kv_dtype)
             else:
                 record = bb // 2 + 4 if config.serialize == "fp8_e4m3" else bb
             self.group_geometry.append(

@@ -26,6 +26,11 @@ built from, for embedding in other MI355X services.
   every page tensor is torch.float16, else bfloat16; pass "float16" /
   "bfloat16" for opaque uint8 views) and every fp8/fp4 method follows it. The
   records are format-free, so the two ends of a transfer need not agree.
+- fp8 pages: a copier over torch.float8_e4m3fn tensors (or uint8 views with
+  kv_dtype="float8_e4m3fn") has the raw and the fp4 methods. A tile then
+  holds block_bytes elements, 16 per lane in the kernels, and an fp4 record
+  is block_bytes/2 + 4*block_bytes/G bytes; loads round to e4m3fn. The
+  *_fp8 and *_fp8_group methods raise ValueError on such a copier.
 - record checksums: packed_bytes*/gather*/scatter* take checksum=True to
   leave a 16-byte footer behind every record; seal_records(ptr, tiles,
   payload_bytes, stream) fills the footers of such a slab and
@@ -41,8 +46,9 @@ def block_copier(groups: Sequence[Sequence], device: Optional[int] = None,
                  kv_dtype: str = "auto"):
     """BlockCopier over torch page tensors (GPU or CPU twins).
 
-    kv_dtype (auto | bfloat16 | float16) is the page format every fp8 and
-    fp4 method of the copier converts with; see offload.engine.resolve_kv_dtype."""
+    kv_dtype (auto | bfloat16 | float16 | float8_e4m3fn) is the page format
+    every fp8 and fp4 method of the copier converts with; see
+    offload.engine.resolve_kv_dtype."""
     from .. import ensure_offload_native
     from ..offload.engine import resolve_kv_dtype
 

@@ -96,7 +96,11 @@ class PeerMigrationService:
         peer.tiered.make_dram_lookup).
         kv_dtype: page format of the fp8 pulls, auto | bfloat16 | float16,
         resolved like OffloadEngineConfig.kv_dtype. fp8 records are
-        format-free, so both ends simply convert with their own value."""
+        format-free, so both ends simply convert with their own value.
+        float8_e4m3fn pages (an fp8 KV cache) are served by raw pulls only:
+        pull(..., fp8=True) and pull_many(..., fp8=True) raise ValueError on
+        such a service, and it answers a peer's fp8 request with raw bytes
+        (the ACK says which arrived)."""
         import torch
         import torch.distributed as dist
 
@@ -179,6 +183,7 @@ class PeerMigrationService:
         blocks to fp8 e4m3 on the fly — half the xGMI bytes, e4m3 rounding
         on the payload (DRAM-cached chunks always travel in their stored
         codec; the ACK says which arrived)."""
+        self._check_fp8_pull(fp8)
         ids = [int(b) for b in dst_block_ids]
         if not ids or len(ids) > 64:
             raise ValueError("dst_block_ids must have 1..64 blocks")
@@ -196,6 +201,7 @@ class PeerMigrationService:
         transfer (small chunks amortize the handshake and the per-transfer
         launch cost). The Future resolves to a list[bool] per chunk (True =
         pulled); raises on timeout/shutdown."""
+        self._check_fp8_pull(fp8)
         if not chunks or len(chunks) > MAX_BATCH:
             raise ValueError(f"pull_many takes 1..{MAX_BATCH} chunks")
         fut: concurrent.futures.Future = concurrent.futures.Future()
@@ -208,6 +214,12 @@ class PeerMigrationService:
             self._cmd_q.append(("pull_many", norm, src_rank,
                                 time.time() + timeout, fut, bool(fp8)))
         return fut
+
+    def _check_fp8_pull(self, fp8: bool) -> None:
+        if fp8 and self.kv_dtype == "float8_e4m3fn":
+            raise ValueError(
+                "fp8=True does not apply to kv_dtype='float8_e4m3fn' pages, "
+                "they already are fp8; pull them raw")
 
     def close(self) -> None:
         """Collective: every rank must call close() (the shutdown protocol
@@ -517,7 +529,9 @@ class PeerMigrationService:
         n_blocks = int(buf[5])
         ok = int(buf[6])
         if op == OP_PULL_REQ:
-            want_fp8 = bool(int(buf[7]))
+            # fp8 pages have no fp8 wire form: such a rank serves raw
+            want_fp8 = (bool(int(buf[7]))
+                        and self.kv_dtype != "float8_e4m3fn")
             ids = self.lookup_local(chunk_hash, group)
             grant = ids is not None and len(ids) == n_blocks
             dram = None
@@ -572,7 +586,9 @@ class PeerMigrationService:
                 self._stats.pulls_failed += 1
                 del pending_pulls[req_id]
         elif op == OP_PULL_REQ_MULTI:
-            want_fp8 = bool(int(buf[7]))
+            # fp8 pages have no fp8 wire form: such a rank serves raw
+            want_fp8 = (bool(int(buf[7]))
+                        and self.kv_dtype != "float8_e4m3fn")
             n_chunks = int(buf[3])
             reqs = []
             for i in range(n_chunks):
