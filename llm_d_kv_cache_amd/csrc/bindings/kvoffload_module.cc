@@ -86,10 +86,12 @@ PYBIND11_MODULE(_kvoffload, m) {
                cfg.serialize = Serialize::kFp8E4M3Group;
              else if (serialize == "fp4_e2m1_group")
                cfg.serialize = Serialize::kFp4E2M1Group;
+             else if (serialize == "fp8_ds_mla")
+               cfg.serialize = Serialize::kFp8DsMla;
              else
                throw std::invalid_argument(
                    "serialize must be "
-                   "raw|fp8_e4m3|fp8_e4m3_group|fp4_e2m1_group");
+                   "raw|fp8_e4m3|fp8_e4m3_group|fp4_e2m1_group|fp8_ds_mla");
              cfg.fp8_group_size = fp8_group_size;
              cfg.fp4_group_size = fp4_group_size;
              cfg.host_cache_bytes = host_cache_bytes;
@@ -282,6 +284,28 @@ PYBIND11_MODULE(_kvoffload, m) {
           py::arg("group"), py::arg("block_ids"), py::arg("src"),
           py::arg("group_size") = 128, py::arg("stream") = 0,
           py::arg("checksum") = false)
+      .def("packed_bytes_fp8_mla", &BlockCopier::packed_bytes_fp8_mla,
+           py::arg("group"), py::arg("n_blocks"), py::arg("checksum") = false)
+      .def(
+          "gather_fp8_mla",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t dst,
+             uintptr_t stream, bool checksum) {
+            py::gil_scoped_release rel;
+            c.gather_fp8_mla(group, ids, reinterpret_cast<void*>(dst), stream,
+                             checksum);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("dst"),
+          py::arg("stream") = 0, py::arg("checksum") = false)
+      .def(
+          "scatter_fp8_mla",
+          [](BlockCopier& c, int group, std::vector<int32_t> ids, uintptr_t src,
+             uintptr_t stream, bool checksum) {
+            py::gil_scoped_release rel;
+            c.scatter_fp8_mla(group, ids, reinterpret_cast<const void*>(src),
+                              stream, checksum);
+          },
+          py::arg("group"), py::arg("block_ids"), py::arg("src"),
+          py::arg("stream") = 0, py::arg("checksum") = false)
       .def("packed_bytes_fp4_group", &BlockCopier::packed_bytes_fp4_group,
            py::arg("group"), py::arg("n_blocks"), py::arg("group_size") = 32,
            py::arg("checksum") = false)

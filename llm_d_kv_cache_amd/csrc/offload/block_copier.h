@@ -12,7 +12,7 @@
 // kv_dtype (bf16 by default) is the format of the pages; every fp8 and fp4
 // method of the copier converts with it, the raw ones never look at it. A
 // copier over fp8 (e4m3fn) pages has the raw and the fp4 methods only: its
-// *_fp8 and *_fp8_group methods throw, the pages already are fp8.
+// *_fp8, *_fp8_group and *_fp8_mla methods throw, the pages already are fp8.
 #pragma once
 
 #include <mutex>
@@ -229,6 +229,65 @@ class BlockCopier {
     if (err != hipSuccess) throw HipError(hipGetErrorString(err));
   }
 
+  // fp8 MLA record size (fp8_mla_format.h): 656 bytes per 1152-byte token
+  // row of the tile.
+  size_t packed_bytes_fp8_mla(int group, size_t n_blocks,
+                              bool checksum = false) const {
+    check_not_fp8_pages();
+    const GroupDesc& g = groups_.at(group);
+    check_mla_tile(g);
+    return n_blocks * g.layer_ptrs.size() *
+           (StorageOffloadEngine::fp8_mla_record_bytes(g.block_bytes) +
+            footer(checksum));
+  }
+
+  // Single-pass gather of MLA rows into dst (device ptr in GPU mode, 16-byte
+  // aligned): latent to fp8 with a scale per 128, RoPE tail copied. Needs no
+  // scratch. Host mode uses the software twin.
+  void gather_fp8_mla(int group, const std::vector<int32_t>& ids, void* dst,
+                      uintptr_t stream, bool checksum = false) {
+    check_not_fp8_pages();
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_mla_tile(g);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp8_mla_copy(
+          g, ids, static_cast<uint8_t*>(dst), /*quantize=*/true,
+          footer(checksum), kv_dtype_);
+      return;
+    }
+    hipError_t err = kvc_launch_gather_fp8_mla(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, ids.data(), static_cast<int>(ids.size()), nullptr,
+        static_cast<uint8_t*>(dst), reinterpret_cast<hipStream_t>(stream),
+        footer(checksum), static_cast<int>(kv_dtype_));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
+  // Dequantize + scatter from an fp8 MLA record slab.
+  void scatter_fp8_mla(int group, const std::vector<int32_t>& ids,
+                       const void* src, uintptr_t stream,
+                       bool checksum = false) {
+    check_not_fp8_pages();
+    const GroupDesc& g = groups_.at(group);
+    check_ids(ids, g);
+    check_mla_tile(g);
+    if (!gpu_mode_) {
+      StorageOffloadEngine::host_fp8_mla_copy(
+          g, ids, const_cast<uint8_t*>(static_cast<const uint8_t*>(src)),
+          /*quantize=*/false, footer(checksum), kv_dtype_);
+      return;
+    }
+    hipError_t err = kvc_launch_scatter_fp8_mla(
+        const_cast<const void* const*>(dev_layer_ptrs_[group]),
+        dev_layer_strides_[group], static_cast<int>(g.layer_ptrs.size()),
+        g.block_bytes, ids.data(), static_cast<int>(ids.size()), nullptr,
+        static_cast<const uint8_t*>(src), reinterpret_cast<hipStream_t>(stream),
+        footer(checksum), static_cast<int>(kv_dtype_));
+    if (err != hipSuccess) throw HipError(hipGetErrorString(err));
+  }
+
   // Group-scaled fp4 (e2m1) record size: n/2 code bytes + one f32 scale per
   // group_size elements, per tile; n = block_bytes/2 elements for 16-bit
   // pages, block_bytes for fp8 pages.
@@ -381,6 +440,14 @@ class BlockCopier {
           "block_bytes/2 = " + std::to_string(g.block_bytes / 2) +
           " elements is not a multiple of fp8 group_size " +
           std::to_string(group_size));
+  }
+
+  static void check_mla_tile(const GroupDesc& g) {
+    if (g.block_bytes == 0 || g.block_bytes % kMlaRowBytes != 0)
+      throw std::invalid_argument(
+          "block_bytes = " + std::to_string(g.block_bytes) +
+          " is not a multiple of the fp8_ds_mla row (" +
+          std::to_string(kMlaRowBytes) + " bytes)");
   }
 
   void check_fp4_group_size(const GroupDesc& g, int group_size) const {

@@ -31,6 +31,7 @@
 #include "checksum.h"
 #include "common.h"
 #include "file_io.h"
+#include "fp8_mla_format.h"
 #include "host_cache.h"
 #include "pcie_mover.h"
 #include "thread_pool.h"
@@ -67,6 +68,14 @@ extern "C" hipError_t kvc_launch_gather_fp8_group(
 extern "C" hipError_t kvc_launch_scatter_fp8_group(
     const void* const*, const uint64_t*, int, uint64_t, int, const int32_t*,
     int, const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
+// fp8 MLA rows (fp8_mla_format.h): the argument lists of the per-tile fp8
+// pair; hipErrorInvalidValue for a tile that 1152 does not divide
+extern "C" hipError_t kvc_launch_gather_fp8_mla(
+    const void* const*, const uint64_t*, int, uint64_t, const int32_t*, int,
+    const int32_t*, uint8_t*, hipStream_t, uint32_t, int);
+extern "C" hipError_t kvc_launch_scatter_fp8_mla(
+    const void* const*, const uint64_t*, int, uint64_t, const int32_t*, int,
+    const int32_t*, const uint8_t*, hipStream_t, uint32_t, int);
 // group-scaled fp4 (e2m1): same argument lists as the fp8-group pair; the
 // only launchers that also take KvDtype::kFp8E4M3 pages (block_bytes elements
 // per tile instead of block_bytes/2)
@@ -113,8 +122,13 @@ enum class CopyPath { kStaged, kZeroCopy, kHostMemcpy };
 // record is [ n fp8 | n/G f32 scales ], n = block_bytes/2. kFp4E2M1Group is
 // the same design one step narrower: OCP e2m1 codes, two per byte, one f32
 // scale per fp4_group_size elements; the record is
-// [ n/2 code bytes | n/G f32 scales ].
-enum class Serialize { kRaw, kFp8E4M3, kFp8E4M3Group, kFp4E2M1Group };
+// [ n/2 code bytes | n/G f32 scales ]. kFp8DsMla is the row-structured codec
+// for DeepSeek MLA pages (fp8_mla_format.h): per 576-element token row the
+// 512 latent values go to fp8 with one scale per 128, the 64 RoPE values are
+// kept bit for bit; 656 bytes per row.
+enum class Serialize {
+  kRaw, kFp8E4M3, kFp8E4M3Group, kFp4E2M1Group, kFp8DsMla
+};
 
 // Format of the KV pages the fp8 and fp4 modes read on store and write on
 // load (raw copies never look at it). The records are format-free; only the
@@ -261,8 +275,9 @@ class StorageOffloadEngine {
       throw std::invalid_argument(
           "fp8_group_size must be 64, 128, 256 or 512 (got " +
           std::to_string(cfg_.fp8_group_size) + ")");
+    const bool mla = cfg_.serialize == Serialize::kFp8DsMla;
     if (cfg_.kv_dtype == KvDtype::kFp8E4M3 &&
-        (grouped || cfg_.serialize == Serialize::kFp8E4M3))
+        (grouped || mla || cfg_.serialize == Serialize::kFp8E4M3))
       throw std::invalid_argument(
           "kv_dtype float8_e4m3fn: the pages already are fp8, so the fp8 "
           "serialize modes do not apply; use raw or fp4_e2m1_group");
@@ -288,6 +303,12 @@ class StorageOffloadEngine {
             std::to_string(g.block_bytes / 2) +
             " elements is not a multiple of fp8_group_size " +
             std::to_string(cfg_.fp8_group_size));
+      if (mla && g.block_bytes % kMlaRowBytes != 0)
+        throw std::invalid_argument(
+            "group " + std::to_string(gi) + ": block_bytes = " +
+            std::to_string(g.block_bytes) +
+            " is not a multiple of the fp8_ds_mla row (" +
+            std::to_string(kMlaRowBytes) + " bytes)");
       if (fp4 &&
           kv_tile_elems(g.block_bytes, cfg_.kv_dtype) % cfg_.fp4_group_size != 0)
         throw std::invalid_argument(
@@ -658,6 +679,8 @@ class StorageOffloadEngine {
       case Serialize::kFp4E2M1Group:
         return fp4_group_record_bytes(g.block_bytes, cfg_.fp4_group_size,
                                       cfg_.kv_dtype);
+      case Serialize::kFp8DsMla:
+        return fp8_mla_record_bytes(g.block_bytes);
       default:
         return g.block_bytes;
     }
@@ -832,6 +855,13 @@ class StorageOffloadEngine {
             dev_layer_strides_[ft.group], nl, g.block_bytes,
             cfg_.fp4_group_size, ft.block_ids.data(), nb, ids_dev, kernel_dst,
             ctx.stream, footer_bytes(), static_cast<int>(cfg_.kv_dtype));
+      } else if (cfg_.serialize == Serialize::kFp8DsMla) {
+        // one wave per token row, single pass, for both destinations
+        err = kvc_launch_gather_fp8_mla(
+            const_cast<const void* const*>(dev_layer_ptrs_[ft.group]),
+            dev_layer_strides_[ft.group], nl, g.block_bytes,
+            ft.block_ids.data(), nb, ids_dev, kernel_dst, ctx.stream,
+            footer_bytes(), static_cast<int>(cfg_.kv_dtype));
       } else if (cfg_.serialize == Serialize::kFp8E4M3) {
         if (cfg_.copy_path == CopyPath::kStaged) {
           // split amax+quantize (chip-filling); the partial-max scratch
@@ -1070,6 +1100,11 @@ class StorageOffloadEngine {
             ptrs, strides, nl, g.block_bytes, cfg_.fp4_group_size,
             ft.block_ids.data(), nb, ids_dev, src, ctx.stream,
             footer_bytes(), static_cast<int>(cfg_.kv_dtype));
+      case Serialize::kFp8DsMla:
+        return kvc_launch_scatter_fp8_mla(ptrs, strides, nl, g.block_bytes,
+                                          ft.block_ids.data(), nb, ids_dev,
+                                          src, ctx.stream, footer_bytes(),
+                                          static_cast<int>(cfg_.kv_dtype));
       case Serialize::kFp8E4M3:
         return kvc_launch_scatter_fp8(ptrs, strides, nl, g.block_bytes,
                                       ft.block_ids.data(), nb, ids_dev, src,
@@ -1269,6 +1304,8 @@ class StorageOffloadEngine {
         else if (cfg_.serialize == Serialize::kFp4E2M1Group)
           fp4_group_quantize_tile(src, g.block_bytes, cfg_.fp4_group_size, out,
                                   cfg_.kv_dtype);
+        else if (cfg_.serialize == Serialize::kFp8DsMla)
+          fp8_mla_quantize_tile(src, g.block_bytes, out, cfg_.kv_dtype);
         else
           std::memcpy(out, src, g.block_bytes);
       }
@@ -1292,6 +1329,8 @@ class StorageOffloadEngine {
         else if (cfg_.serialize == Serialize::kFp4E2M1Group)
           fp4_group_dequantize_tile(in, g.block_bytes, cfg_.fp4_group_size, dst,
                                     cfg_.kv_dtype);
+        else if (cfg_.serialize == Serialize::kFp8DsMla)
+          fp8_mla_dequantize_tile(in, g.block_bytes, dst, cfg_.kv_dtype);
         else
           std::memcpy(dst, in, g.block_bytes);
       }
@@ -1509,6 +1548,32 @@ class StorageOffloadEngine {
     }
   }
 
+  static size_t fp8_mla_record_bytes(uint64_t block_bytes) {
+    return static_cast<size_t>(block_bytes / kMlaRowBytes) * kMlaEntryBytes;
+  }
+
+  // Software twin of kvc_gather_fp8_mla / kvc_scatter_fp8_mla (engine host
+  // mode and BlockCopier's CPU path): same bytes as the kernels.
+  static void host_fp8_mla_copy(const GroupDesc& g,
+                                const std::vector<int32_t>& ids,
+                                uint8_t* packed, bool quantize,
+                                size_t footer = 0,
+                                KvDtype kv_dtype = KvDtype::kBf16) {
+    const size_t nl = g.layer_ptrs.size();
+    const size_t rec = fp8_mla_record_bytes(g.block_bytes) + footer;
+    for (size_t bi = 0; bi < ids.size(); ++bi) {
+      for (size_t l = 0; l < nl; ++l) {
+        uint8_t* page = static_cast<uint8_t*>(g.layer_ptrs[l]) +
+                        static_cast<uint64_t>(ids[bi]) * g.layer_strides[l];
+        uint8_t* slab = packed + (bi * nl + l) * rec;
+        if (quantize)
+          fp8_mla_quantize_tile(page, g.block_bytes, slab, kv_dtype);
+        else
+          fp8_mla_dequantize_tile(slab, g.block_bytes, page, kv_dtype);
+      }
+    }
+  }
+
   private:
   // Record starts are only 4-byte aligned and scales follow n payload
   // bytes: scales move through memcpy.
@@ -1543,6 +1608,36 @@ class StorageOffloadEngine {
       std::memcpy(&scale, in + n + 4 * gi, 4);
       for (size_t i = 0; i < G; ++i)
         out[gi * G + i] = T::from_f32(fp8_to_f32(in[gi * G + i]) * scale);
+    }
+  }
+
+  // fp8_ds_mla: the first 528 bytes of a row's entry, [ 512 codes | 4 f32
+  // scales ], are exactly the fp8-group record of the row's 512 latent values
+  // at G = 128, so each row goes through the grouped codec above; the 64
+  // RoPE values behind them move as bytes and never become a float.
+  template <typename T>
+  static void fp8_mla_quantize_tile_t(const uint8_t* src, size_t block_bytes,
+                                      uint8_t* out) {
+    for (size_t r = 0; r < block_bytes / kMlaRowBytes; ++r) {
+      const uint8_t* row = src + r * kMlaRowBytes;
+      uint8_t* entry = out + r * kMlaEntryBytes;
+      fp8_group_quantize_tile_t<T>(row, 2 * kMlaLatentElems, kMlaGroupElems,
+                                   entry);
+      std::memcpy(entry + kMlaRopeOffset, row + 2 * kMlaLatentElems,
+                  2 * kMlaRopeElems);
+    }
+  }
+
+  template <typename T>
+  static void fp8_mla_dequantize_tile_t(const uint8_t* in, size_t block_bytes,
+                                        uint8_t* dst) {
+    for (size_t r = 0; r < block_bytes / kMlaRowBytes; ++r) {
+      const uint8_t* entry = in + r * kMlaEntryBytes;
+      uint8_t* row = dst + r * kMlaRowBytes;
+      fp8_group_dequantize_tile_t<T>(entry, 2 * kMlaLatentElems,
+                                     kMlaGroupElems, row);
+      std::memcpy(row + 2 * kMlaLatentElems, entry + kMlaRopeOffset,
+                  2 * kMlaRopeElems);
     }
   }
 
@@ -1685,6 +1780,20 @@ class StorageOffloadEngine {
       fp8_group_dequantize_tile_t<PageFp16>(in, block_bytes, group_size, dst);
     else
       fp8_group_dequantize_tile_t<PageBf16>(in, block_bytes, group_size, dst);
+  }
+  static void fp8_mla_quantize_tile(const uint8_t* src, size_t block_bytes,
+                                    uint8_t* out, KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_mla_quantize_tile_t<PageFp16>(src, block_bytes, out);
+    else
+      fp8_mla_quantize_tile_t<PageBf16>(src, block_bytes, out);
+  }
+  static void fp8_mla_dequantize_tile(const uint8_t* in, size_t block_bytes,
+                                      uint8_t* dst, KvDtype kv_dtype) {
+    if (kv_dtype == KvDtype::kFp16)
+      fp8_mla_dequantize_tile_t<PageFp16>(in, block_bytes, dst);
+    else
+      fp8_mla_dequantize_tile_t<PageBf16>(in, block_bytes, dst);
   }
   static void fp4_group_quantize_tile(const uint8_t* src, size_t block_bytes,
                                       int group_size, uint8_t* out,

@@ -28,6 +28,8 @@
 
 #include <cstdint>
 
+#include "fp8_mla_format.h"
+
 namespace kvo {
 
 constexpr int kMaxBlocksPerFile = 128;   // by-value kernarg limit
@@ -774,6 +776,216 @@ extern "C" hipError_t kvc_launch_scatter_fp8_group(
       hipLaunchKernelGGL(kvc_scatter_fp8_group<T>, grid, dim3(256), 0, stream,
                          layer_ptrs_dev, layer_strides_dev, num_layers,
                          block_bytes, shift, bl, ids_dev, src, footer_bytes));
+  return hipGetLastError();
+}
+
+// ---- fp8 MLA rows (latent in fp8, RoPE tail verbatim) -----------------------
+// serialize="fp8_ds_mla": the tile is rows = block_bytes/1152 token rows of
+// 576 16-bit elements, 512 latent values then 64 RoPE key values; the record
+// is one 656-byte entry per row (fp8_mla_format.h):
+//   [ 512 e4m3fn codes | 4 f32 scales (one per 128 latent) | 64 x 16 bit ]
+// The latent arithmetic is that of fp8_e4m3_group at G = 128; the RoPE tail
+// never passes through a float, it moves as uint4.
+//
+// A row is 72 16-byte vectors, 64 to quantize and 8 to copy, so the flat
+// v -> lane mapping of the kernels above would let wave and group
+// boundaries drift through the rows. Here ONE WAVE OWNS ONE ROW: lane i
+// takes latent vector i (8 values), a scale group is lanes 16g..16g+15, the
+// group amax is a four-step xor butterfly, and lanes 0..7 also carry the
+// eight tail vectors. A wave reads 1152 contiguous bytes and writes 656
+// contiguous bytes (the scatter the reverse). Single pass, no LDS, no
+// scratch, so the same kernel serves the staged and the zero-copy
+// destination.
+//
+// Grid: tile on blockIdx.x, row slices on blockIdx.y, four rows (waves) per
+// 256-thread workgroup. The row index is wave-uniform, so a wave either runs
+// a trip of the loop with all 64 lanes or not at all: no dead lanes reach a
+// shuffle.
+
+template <typename T>
+__global__ __launch_bounds__(256) void kvc_gather_fp8_mla(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, uint8_t* __restrict__ dst,
+    uint32_t footer_bytes) {
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint32_t rows = static_cast<uint32_t>(block_bytes / kMlaRowBytes);
+  const uint64_t record =
+      static_cast<uint64_t>(rows) * kMlaEntryBytes + footer_bytes;
+  const uint8_t* __restrict__ page =
+      static_cast<const uint8_t*>(layer_ptrs[l]) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l];
+  uint8_t* __restrict__ payload = dst + static_cast<uint64_t>(tile) * record;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (uint32_t r = blockIdx.y * 4 + wave; r < rows; r += gridDim.y * 4) {
+    const uint4* __restrict__ row = reinterpret_cast<const uint4*>(
+        page + static_cast<uint64_t>(r) * kMlaRowBytes);
+    uint8_t* __restrict__ entry =
+        payload + static_cast<uint64_t>(r) * kMlaEntryBytes;
+    const uint4 w = row[lane];
+    uint4 tail = make_uint4(0, 0, 0, 0);
+    if (lane < kMlaRopeElems / 8) tail = row[kMlaLatentElems / 8 + lane];
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(&w);
+    float x[8];
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[2 * j] = T::to_f32(static_cast<uint16_t>(dw[j]));
+      x[2 * j + 1] = T::to_f32(static_cast<uint16_t>(dw[j] >> 16));
+      amax = fmaxf(amax, fmaxf(fabsf(x[2 * j]), fabsf(x[2 * j + 1])));
+    }
+#pragma unroll
+    for (int off = kMlaGroupElems / 16; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    if (amax <= 0.0f) amax = 1.0f;
+    const float inv_scale = kFp8Max / amax;
+    uint32_t lo = 0, hi = 0;
+    // word_sel must be an immediate: unrolled by hand
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv_scale, x[1] * inv_scale, lo, 0);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv_scale, x[3] * inv_scale, lo, 1);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4] * inv_scale, x[5] * inv_scale, hi, 0);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv_scale, x[7] * inv_scale, hi, 1);
+    reinterpret_cast<uint2*>(entry)[lane] = make_uint2(lo, hi);
+    if ((lane & (kMlaGroupElems / 8 - 1)) == 0)
+      reinterpret_cast<float*>(entry + kMlaScaleOffset)[lane / (kMlaGroupElems / 8)] =
+          amax / kFp8Max;
+    if (lane < kMlaRopeElems / 8)
+      reinterpret_cast<uint4*>(entry + kMlaRopeOffset)[lane] = tail;
+  }
+}
+
+// Mirror of the gather: lane i reads its uint2 of codes and the scale of
+// its 16-lane group (one address per group, an L2-hit load), dequantizes to
+// one uint4 of page values; lanes 0..7 copy the tail back.
+template <typename T>
+__global__ __launch_bounds__(256) void kvc_scatter_fp8_mla(
+    const void* const* __restrict__ layer_ptrs,
+    const uint64_t* __restrict__ layer_strides, int num_layers,
+    uint64_t block_bytes, BlockList blocks,
+    const int32_t* __restrict__ ids_dev, const uint8_t* __restrict__ src,
+    uint32_t footer_bytes) {
+  const uint32_t tile = blockIdx.x;
+  const int l = tile % num_layers;
+  const int bi = tile / num_layers;
+  const uint32_t rows = static_cast<uint32_t>(block_bytes / kMlaRowBytes);
+  const uint64_t record =
+      static_cast<uint64_t>(rows) * kMlaEntryBytes + footer_bytes;
+  uint8_t* __restrict__ page =
+      static_cast<uint8_t*>(const_cast<void*>(layer_ptrs[l])) +
+      static_cast<uint64_t>(block_id(blocks, ids_dev, bi)) * layer_strides[l];
+  const uint8_t* __restrict__ payload =
+      src + static_cast<uint64_t>(tile) * record;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (uint32_t r = blockIdx.y * 4 + wave; r < rows; r += gridDim.y * 4) {
+    uint4* __restrict__ row = reinterpret_cast<uint4*>(
+        page + static_cast<uint64_t>(r) * kMlaRowBytes);
+    const uint8_t* __restrict__ entry =
+        payload + static_cast<uint64_t>(r) * kMlaEntryBytes;
+    const uint2 w = reinterpret_cast<const uint2*>(entry)[lane];
+    const float scale = reinterpret_cast<const float*>(
+        entry + kMlaScaleOffset)[lane / (kMlaGroupElems / 8)];
+    uint4 tail = make_uint4(0, 0, 0, 0);
+    if (lane < kMlaRopeElems / 8)
+      tail = reinterpret_cast<const uint4*>(entry + kMlaRopeOffset)[lane];
+    uint4 o;
+    uint32_t* od = reinterpret_cast<uint32_t*>(&o);
+    const uint32_t words[2] = {w.x, w.y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint8_t b0 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16));
+      uint8_t b1 = static_cast<uint8_t>(words[j >> 1] >> ((j & 1) * 16 + 8));
+      uint16_t h0 = T::from_f32(fp8_e4m3_to_f32(b0) * scale);
+      uint16_t h1 = T::from_f32(fp8_e4m3_to_f32(b1) * scale);
+      od[j] = static_cast<uint32_t>(h0) | (static_cast<uint32_t>(h1) << 16);
+    }
+    row[lane] = o;
+    if (lane < kMlaRopeElems / 8) row[kMlaLatentElems / 8 + lane] = tail;
+  }
+}
+
+namespace {
+
+// Rows per tile, or 0 for a tile that 1152 does not divide.
+inline uint32_t fp8_mla_rows(uint64_t block_bytes) {
+  if (block_bytes == 0 || block_bytes % kMlaRowBytes != 0 ||
+      block_bytes / kMlaRowBytes > 0xffffffffull)
+    return 0;
+  return static_cast<uint32_t>(block_bytes / kMlaRowBytes);
+}
+
+// copy_grid sizes slices by 256 vectors; this pair works in rows, four per
+// workgroup: at most ceil(rows/4) workgroups per tile, otherwise the same
+// ">= 2048 workgroups when the transfer is large enough" rule, then the
+// fewest workgroups that keep that many trips of the row loop, so every
+// slice makes the same number of trips. At the MLA preset (976 tiles of 16
+// rows) the plain rule gives 3 slices, of which slice 0 alone makes a second
+// trip; 2 slices of two trips each measured 3 % faster
+// (profiles/fp8_ds_mla_kernels.md).
+inline dim3 mla_grid(uint32_t tiles, uint32_t rows) {
+  uint32_t max_wg_per_tile = (rows + 3) / 4;  // cap: one row per wave
+  uint32_t want = tiles >= 2048 ? 1 : (2048 + tiles - 1) / tiles;
+  uint32_t wg_per_tile = want < max_wg_per_tile ? want : max_wg_per_tile;
+  if (wg_per_tile == 0) wg_per_tile = 1;
+  if (wg_per_tile > 65535) wg_per_tile = 65535;  // y-dimension limit
+  const uint32_t trips = (max_wg_per_tile + wg_per_tile - 1) / wg_per_tile;
+  wg_per_tile = (max_wg_per_tile + trips - 1) / trips;
+  return dim3(tiles, wg_per_tile);
+}
+
+}  // namespace
+
+extern "C" hipError_t kvc_launch_gather_fp8_mla(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, const int32_t* block_ids,
+    int num_blocks, const int32_t* ids_dev, uint8_t* dst, hipStream_t stream,
+    uint32_t footer_bytes, int kv_dtype) {
+  const uint32_t rows = fp8_mla_rows(block_bytes);
+  // entries are written as uint2/uint4: the slab and the footer keep them
+  // 16-byte aligned
+  if (rows == 0 || reinterpret_cast<uintptr_t>(dst) % 16 != 0 ||
+      footer_bytes % 16 != 0)
+    return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = mla_grid(tiles, rows);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_gather_fp8_mla<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, dst, footer_bytes));
+  return hipGetLastError();
+}
+
+extern "C" hipError_t kvc_launch_scatter_fp8_mla(
+    const void* const* layer_ptrs_dev, const uint64_t* layer_strides_dev,
+    int num_layers, uint64_t block_bytes, const int32_t* block_ids,
+    int num_blocks, const int32_t* ids_dev, const uint8_t* src,
+    hipStream_t stream, uint32_t footer_bytes, int kv_dtype) {
+  const uint32_t rows = fp8_mla_rows(block_bytes);
+  if (rows == 0 || reinterpret_cast<uintptr_t>(src) % 16 != 0 ||
+      footer_bytes % 16 != 0)
+    return hipErrorInvalidValue;
+  BlockList bl;
+  if (ids_dev == nullptr) {
+    if (num_blocks > kMaxBlocksPerFile) return hipErrorInvalidValue;
+    for (int i = 0; i < num_blocks; ++i) bl.ids[i] = block_ids[i];
+  }
+  uint32_t tiles = static_cast<uint32_t>(num_blocks) * num_layers;
+  dim3 grid = mla_grid(tiles, rows);
+  KVC_WITH_PAGE_TYPE(
+      kv_dtype,
+      hipLaunchKernelGGL(kvc_scatter_fp8_mla<T>, grid, dim3(256), 0, stream,
+                         layer_ptrs_dev, layer_strides_dev, num_layers,
+                         block_bytes, bl, ids_dev, src, footer_bytes));
   return hipGetLastError();
 }
 

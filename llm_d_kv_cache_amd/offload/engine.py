@@ -26,6 +26,9 @@ class OffloadEngineConfig:
     # | fp8_e4m3_group (fp8 + one scale per fp8_group_size elements)
     # | fp4_e2m1_group (4-bit e2m1 codes, two per byte, + one scale per
     #   fp4_group_size elements; lossy at 4 bits, model quality unmeasured)
+    # | fp8_ds_mla (DeepSeek MLA pages of 576-element token rows: the 512
+    #   latent values as fp8 + one scale per 128, the 64 RoPE values kept
+    #   bit for bit; 656 bytes per 1152-byte row, fixed geometry)
     serialize: str = "raw"
     # elements per scale for fp8_e4m3_group (set it to head_dim); one of
     # 64/128/256/512, ignored by the other modes
@@ -53,9 +56,14 @@ class OffloadEngineConfig:
     kv_dtype: str = "auto"
 
 
-SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group", "fp4_e2m1_group")
+SERIALIZE_MODES = ("raw", "fp8_e4m3", "fp8_e4m3_group", "fp4_e2m1_group",
+                   "fp8_ds_mla")
 FP8_GROUP_SIZES = (64, 128, 256, 512)
 FP4_GROUP_SIZES = (16, 32, 64, 128)
+# fp8_ds_mla geometry (csrc/offload/fp8_mla_format.h): a token row of 576
+# 16-bit elements becomes [512 e4m3 | 4 f32 scales | 64 x 16 bit verbatim]
+MLA_ROW_BYTES = 1152
+MLA_ENTRY_BYTES = 656
 CHECKSUM_FOOTER_BYTES = 16
 CHECKSUM_MAGIC = 0x5343564B  # the bytes "KVCS"
 # suffix of the FileMapper dtype tag that keeps checksummed files apart
@@ -121,7 +129,8 @@ def check_serialize_kv_dtype(serialize: str, kv_dtype: str) -> None:
     """float8_e4m3fn pages already are fp8: the fp8 modes raise ValueError on
     them. ``kv_dtype`` is a resolved value (resolve_kv_dtype)."""
     if kv_dtype == "float8_e4m3fn" and serialize in ("fp8_e4m3",
-                                                     "fp8_e4m3_group"):
+                                                     "fp8_e4m3_group",
+                                                     "fp8_ds_mla"):
         raise ValueError(
             f"serialize={serialize!r} does not apply to kv_dtype="
             "'float8_e4m3fn' pages, they already are fp8; use 'raw' or "
@@ -139,10 +148,13 @@ def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
     fp4_e2m1_group: n/2 + 4*n/G with G = fp4_group_size (two e2m1 codes per
     byte). kv_dtype is the resolved page format: with "float8_e4m3fn" a tile
     holds n = block_bytes elements, so fp4_e2m1_group gives block_bytes/2 +
-    4*block_bytes/G; the fp8 modes raise on such pages. checksum=True adds
+    4*block_bytes/G; the fp8 modes raise on such pages. fp8_ds_mla: 656 per
+    1152-byte token row (512 fp8 codes, 4 f32 scales, 128 bytes copied), the
+    group sizes are ignored. checksum=True adds
     the 16-byte footer (sum u64, magic, payload bytes). Raises ValueError
     for an unknown mode or page format, a group size outside FP8_GROUP_SIZES
-    (FP4_GROUP_SIZES for fp4), or a KV group whose tile G does not divide.
+    (FP4_GROUP_SIZES for fp4), or a KV group whose tile G (for fp8_ds_mla:
+    the 1152-byte row) does not divide.
     """
     if kv_dtype not in KV_DTYPES:
         raise ValueError(
@@ -153,6 +165,13 @@ def tile_record_bytes(serialize: str, block_bytes: int, fp8_group_size: int,
         return block_bytes + footer
     if serialize == "fp8_e4m3":
         return block_bytes // 2 + 4 + footer
+    if serialize == "fp8_ds_mla":
+        if block_bytes <= 0 or block_bytes % MLA_ROW_BYTES != 0:
+            raise ValueError(
+                f"KV group {group}: block_bytes={block_bytes} is not a "
+                f"multiple of the fp8_ds_mla token row ({MLA_ROW_BYTES} "
+                "bytes: 512 latent + 64 RoPE 16-bit elements)")
+        return block_bytes // MLA_ROW_BYTES * MLA_ENTRY_BYTES + footer
     if serialize == "fp4_e2m1_group":
         if fp4_group_size not in FP4_GROUP_SIZES:
             raise ValueError(
@@ -246,7 +265,8 @@ class TorchOffloadEngine:
             # canonical layouts are dense so stride == payload
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
             footer = CHECKSUM_FOOTER_BYTES if config.checksum else 0
-            if config.serialize in ("fp8_e4m3_group", "fp4_e2m1_group"):
+            if config.serialize in ("fp8_e4m3_group", "fp4_e2m1_group",
+                                    "fp8_ds_mla"):
                 record_bytes = tile_record_bytes(
                     config.serialize, bb, config.fp8_group_size, gi,
                     config.checksum, config.fp4_group_size,
@@ -369,7 +389,8 @@ class TorchOffloadEngine:
         entry. The payload layout matches the file layout (raw gather
         layout, per-tile fp8 records when serialize="fp8_e4m3", group-scaled
         fp8 records when serialize="fp8_e4m3_group", group-scaled fp4
-        records when serialize="fp4_e2m1_group"). With checksum=True
+        records when serialize="fp4_e2m1_group", 656-byte row entries when
+        serialize="fp8_ds_mla"). With checksum=True
         every record in the returned slab still carries its 16-byte footer
         (record stride = group_geometry[group]["record_bytes"]); the slab is
         handed out as stored, it is not verified here."""

@@ -30,8 +30,8 @@ class ObjStorageConfig:
     bucket: str = "kvcache"
     io_threads: int = 8
     timeout_s: float = 30.0
-    # raw | fp8_e4m3 | fp8_e4m3_group | fp4_e2m1_group (via the native codec
-    # kernels)
+    # raw | fp8_e4m3 | fp8_e4m3_group | fp4_e2m1_group | fp8_ds_mla (via the
+    # native codec kernels)
     serialize: str = "raw"
     fp8_group_size: int = 128  # elements per scale, fp8_e4m3_group only
     fp4_group_size: int = 32  # elements per scale, fp4_e2m1_group only
@@ -179,6 +179,7 @@ class ObjStorageEngine:
         self.group_geometry: List[dict] = []
         self._fp8_group = config.serialize == "fp8_e4m3_group"
         self._fp4_group = config.serialize == "fp4_e2m1_group"
+        self._fp8_mla = config.serialize == "fp8_ds_mla"
         self._group_size = (config.fp4_group_size if self._fp4_group
                             else config.fp8_group_size)
         for gi, g in enumerate(groups):
@@ -186,7 +187,7 @@ class ObjStorageEngine:
             strides = [t.stride(0) * t.element_size() for t in g]
             bb = strides[0]
             native_groups.append((ptrs, strides, bb, int(g[0].shape[0])))
-            if self._fp8_group or self._fp4_group:
+            if self._fp8_group or self._fp4_group or self._fp8_mla:
                 record = tile_record_bytes(
                     config.serialize, bb, config.fp8_group_size, gi,
                     fp4_group_size=config.fp4_group_size,
@@ -220,6 +221,8 @@ class ObjStorageEngine:
         if self._fp8_group:
             return self._copier.packed_bytes_fp8_group(group, n_blocks,
                                                        self._group_size)
+        if self._fp8_mla:
+            return self._copier.packed_bytes_fp8_mla(group, n_blocks)
         if self._fp8:
             return self._copier.packed_bytes_fp8(group, n_blocks)
         return self._copier.packed_bytes(group, n_blocks)
@@ -249,6 +252,9 @@ class ObjStorageEngine:
                     self._copier.gather_fp8_group(group, ids, dev.data_ptr(),
                                                   self._group_size,
                                                   stream.cuda_stream)
+                elif self._fp8_mla:
+                    self._copier.gather_fp8_mla(group, ids, dev.data_ptr(),
+                                                stream.cuda_stream)
                 elif self._fp8:
                     self._copier.gather_fp8(group, ids, dev.data_ptr(),
                                             dev.data_ptr() + nb,
@@ -267,6 +273,8 @@ class ObjStorageEngine:
             elif self._fp8_group:
                 self._copier.gather_fp8_group(group, ids, host.data_ptr(),
                                               self._group_size, 0)
+            elif self._fp8_mla:
+                self._copier.gather_fp8_mla(group, ids, host.data_ptr(), 0)
             elif self._fp8:
                 self._copier.gather_fp8(group, ids, host.data_ptr(), 0, 0)
             else:
@@ -290,6 +298,8 @@ class ObjStorageEngine:
             def scatter(group, ids, src, stream):
                 self._copier.scatter_fp8_group(group, ids, src,
                                                self._group_size, stream)
+        elif self._fp8_mla:
+            scatter = self._copier.scatter_fp8_mla
         elif self._fp8:
             scatter = self._copier.scatter_fp8
         else:

@@ -21,6 +21,13 @@ built from, for embedding in other MI355X services.
   shape as the fp8-group pair, no scratch. Lossy at 4 bits; the effect on
   model quality has not been measured. serialize="fp4_e2m1_group" rides
   these kernels.
+- fp8 MLA rows: gather_fp8_mla / scatter_fp8_mla (sized by
+  packed_bytes_fp8_mla) serialize DeepSeek MLA pages, runs of 576-element
+  token rows: the 512 latent values become e4m3 codes with one f32 scale per
+  128, the 64 RoPE key values are copied bit for bit; 656 bytes per
+  1152-byte row, no group-size argument. One wave per row, single pass, no
+  scratch; block_bytes must be a multiple of 1152 and the slab 16-byte
+  aligned. serialize="fp8_ds_mla" rides these kernels.
 - page format: the fp8 families and the fp4 pair convert bf16 or fp16 pages. The copier is
   built for one format (block_copier(..., kv_dtype="auto"): float16 if
   every page tensor is torch.float16, else bfloat16; pass "float16" /
@@ -30,7 +37,8 @@ built from, for embedding in other MI355X services.
   kv_dtype="float8_e4m3fn") has the raw and the fp4 methods. A tile then
   holds block_bytes elements, 16 per lane in the kernels, and an fp4 record
   is block_bytes/2 + 4*block_bytes/G bytes; loads round to e4m3fn. The
-  *_fp8 and *_fp8_group methods raise ValueError on such a copier.
+  *_fp8, *_fp8_group and *_fp8_mla methods raise ValueError on such a
+  copier.
 - record checksums: packed_bytes*/gather*/scatter* take checksum=True to
   leave a 16-byte footer behind every record; seal_records(ptr, tiles,
   payload_bytes, stream) fills the footers of such a slab and
